@@ -16,8 +16,15 @@ itself: `python bench.py --gpus N`) meet over a Unix-domain socket -- RCCL id, b
 exchange is RCCL behind the C-ABI: no rank imports torch.
 
 Prints ONE JSON line (rank 0).  Extra objects: `roofline` (algorithmic HBM bytes of the fused launch / measured
-kernel time, HIP events on the launch stream) and `cpu_baseline` (the CPU oracle timed on this host's cores on a
-bounded sample of the same workload; N = 1 only).
+kernel time, HIP events on the launch stream) and, with --full, `cpu_baseline` (the CPU oracle timed on this host's
+cores on a bounded sample of the same workload; N = 1 only).
+
+A plain run sets up, warms up, times the K steps and prints its line.  --full adds every figure beyond the headline:
+the CPU baseline before the GPU work, and after the clock stops the host-array interface, the round-4 configuration,
+BASELINE.md's 1000-step rollout and step_until_convergence (N = 1), or the same steps without the exchange (N > 1).
+--dump-outputs DIR writes what the timed path computed in its last step (observation, info flags, gripper width,
+substeps; the task's outputs and depth frames where they run) as DIR/<name>.npy, float64 (depth frames float32).
+The inputs are drawn from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 
 from __future__ import annotations
@@ -39,6 +46,29 @@ ALGO_BYTES_PER_ENV_STEP = 1292
 ALGO_FLOP_PER_SUBSTEP = 1.0e4  # SURVEY 8(d) estimate of MuJoCo's pipeline for this scene
 HBM_PEAK_GBS = 8000.0
 FP64_VECTOR_PEAK_TFLOPS = 78.6
+DUMP_BYTES = 60 << 20  # --dump-outputs: the files' payload in all (64 MB less headroom for the .npy headers)
+
+
+def write_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array (environments on its first axis) as out_dir/<name>.npy.  Where the whole would pass
+    DUMP_BYTES, an array that does not fit its share is cut to a fixed sample of environments (numpy seed 0), whose indices
+    go to <name>_envs.npy."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BYTES
+    names = sorted(arrays, key=lambda k: arrays[k].nbytes)
+    for i, name in enumerate(names):
+        a = arrays[name]
+        share = left // (len(names) - i)  # what is left, split evenly over this array and the larger ones
+        if a.nbytes > share:
+            k = max(1, share // (a.nbytes // a.shape[0] + 8))
+            envs = np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False)).astype(np.float64)
+            np.save(os.path.join(out_dir, name + "_envs.npy"), envs)
+            a = a[envs.astype(np.int64)]
+            left -= envs.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def cpu_baseline_worker(n_envs: int, n_steps: int, seed0: int) -> None:
@@ -153,8 +183,13 @@ def main() -> None:
     ap.add_argument("--cameras", default="", help="comma-separated MJCF camera names: one depth frame (uint16 mm, ray-cast) per camera per "
                                                  "env-step, inside the timed region (SimCameraSet, render on demand); not the headline")
     ap.add_argument("--resolution", default="256x256", help="WxH of the depth frames (FR3SimplePickUpSimEnvCreator default 256x256)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the figures taken after the clock stops (host API, round-4 configuration, BASELINE.md's 1000-step rollout, step_until_convergence): profiling runs")
+    ap.add_argument("--full", action="store_true",
+                    help="every figure beyond the headline: the CPU baseline, and after the clock stops the host API, the round-4 configuration, "
+                         "BASELINE.md's 1000-step rollout, step_until_convergence (N = 1) or the steps without the exchange (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64; depth frames float32), 64 MB at most")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the figures taken after the clock stops (host API, round-4 configuration, BASELINE.md's 1000-step rollout, step_until_convergence): profiling runs")
     ap.add_argument("--clock-warmup-ms", type=float, default=25.0,
                     help="before the W warmup steps: this many milliseconds of the same env-step launches, then a reset -- the device needs "
                          "~12 ms of work to reach its operating clocks (profiles/README.md: a launch takes 128 us at first, 112.5 us from "
@@ -175,6 +210,8 @@ def main() -> None:
     if args.cpu_baseline_worker:
         cpu_baseline_worker(*(int(x) for x in args.cpu_baseline_worker))
         return
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher of N ranks, one per GPU (what the driver's
@@ -197,7 +234,7 @@ def main() -> None:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: launch one rank per GPU (or run `python bench.py --gpus N`, which spawns them)")
 
     cpu_base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_base = run_cpu_baseline()  # before any GPU context exists in this process
 
     import ctypes as C
@@ -469,16 +506,27 @@ def main() -> None:
     device_sync()
     rdv.barrier()
     elapsed = time.perf_counter() - t0
-    obs_host = obs.download()
+    obs_host = obs_seen = obs.download()
     if exchange:  # (after the clock stopped) this rank's rows of the last gathered tensor: finiteness check below
-        obs_host = np.asarray(exchange.gathered(T - 1))[rank * n:(rank + 1) * n]
+        obs_seen = np.asarray(exchange.gathered(T - 1))
+        obs_host = obs_seen[rank * n:(rank + 1) * n]
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step (with N > 1: the gathered observation, this rank's other outputs),
+        # read before anything below reuses these buffers
+        dump = {"obs": obs_seen, "info": info.download().astype(np.float64), "gripper_width": gw.download(),
+                "substeps": sub.download().astype(np.float64)}
+        if task_out is not None:
+            dump["task"] = task_out.download()
+        for c, buf in cam_out.items():
+            dump["depth_" + c] = buf.download().astype(np.float32)
+        write_outputs(args.dump_outputs, dump)
     elapsed = rdv.reduce(elapsed, max)
 
     kernel_ms = ms.value / max(launches.value, 1)
     # N > 1: the same K steps once more WITHOUT the exchange (after the clock stopped; reported next to the measured value, never
     # as it) -- what the all-gather costs a step on this node, i.e. how much of a scaling loss is the exchange's and how much the shards'
     no_exchange_value = exchange_ms = None
-    if world > 1 and exchange is not None and not episode:
+    if args.full and world > 1 and exchange is not None and not episode:
         saved_exchange, exchange = exchange, None
         device_sync()
         rdv.barrier()
@@ -520,7 +568,7 @@ def main() -> None:
     # copies and a stream synchronise per step) -- after the clock stopped, reported next to `value`, never as it.
     value_host_api = None
     headline_cfg = (args.mode == "async" and args.task == "none" and args.robot == "fr3" and args.control == "joints" and not mixed and not cam_out and world == 1)
-    headline_cfg = headline_cfg and not args.no_extras
+    headline_cfg = headline_cfg and args.full and not args.no_extras
     if headline_cfg and rank == 0:
         a_host = (np.random.default_rng(7).random((32, n, env.dof)) * 2 - 1) * MAX_JOINT_MOV
         g_host = np.random.default_rng(8).random((32, n)).astype(np.float32)

@@ -305,12 +305,24 @@ def run_pick_task_parity(n_envs=16, n_steps=6, seed=0, episodes=2, async_control
     return rep
 
 
+_SCRATCH = None
+
+
+def scratch_dir() -> str:
+    """A temporary directory of this process's own for the derived scenes the tests write (a fixed name under the shared
+    temporary directory may belong to another user, or hold another checkout's copy)."""
+    global _SCRATCH
+    if _SCRATCH is None:
+        import tempfile
+
+        _SCRATCH = tempfile.mkdtemp(prefix="rcs_amd_")
+    return _SCRATCH
+
+
 def xarm7_frictionless_scene() -> str:
     """The xArm7 scene with frictionloss = 0, written to a temporary file: a 7-dof arm without gripper and WITHOUT dry friction
     rows -- the `Topo<7, false>` kernels without the friction variant, which no shipped scene selects."""
-    import tempfile
-
-    path = os.path.join(tempfile.gettempdir(), "rcs_amd_xarm7_frictionless", "scene.xml")
+    path = os.path.join(scratch_dir(), "rcs_amd_xarm7_frictionless", "scene.xml")
     if not os.path.exists(path):
         os.makedirs(os.path.dirname(path), exist_ok=True)
         xml = open(XARM7_SCENE).read()
@@ -323,10 +335,9 @@ def fr3_arm_only_scene() -> str:
     """The FR3 scene without its hand (hand, camera body, fingers, gripper actuator, tendon and equality removed), written to a
     temporary file: 7 dofs and NO constraint row away from the joint limits, so one substep is the smooth system alone --
     what tests/golden/fr3_arm_dynamics.json (tools/derive_fr3_dynamics.py) predicts from first principles."""
-    import tempfile
     import xml.etree.ElementTree as ET
 
-    path = os.path.join(tempfile.gettempdir(), "rcs_amd_fr3_arm_only", "scene.xml")
+    path = os.path.join(scratch_dir(), "rcs_amd_fr3_arm_only", "scene.xml")
     if not os.path.exists(path):
         os.makedirs(os.path.dirname(path), exist_ok=True)
         tree = ET.parse(SCENE)
@@ -355,11 +366,9 @@ def scene_with_joint_friction(robot: str) -> str:
     """The FR3 / arm6 scene with dry joint friction on every joint (frictionloss = 0.5), written to a temporary file: the
     friction-row kernels for the archetypes whose shipped scenes have none -- FR3 + hand (friction rows next to the coupling
     equality, the finger limits and the tendon actuator) and the 6-dof arm."""
-    import tempfile
-
     src, old, new = {"fr3_fric": (SCENE, '<joint armature="0.1" damping="1"/>', '<joint armature="0.1" damping="1" frictionloss="0.5"/>'),
                      "arm6_fric": (ARM6_SCENE, 'range="-6.28319 6.28319" damping="2"/>', 'range="-6.28319 6.28319" damping="2" frictionloss="0.5"/>')}[robot]
-    path = os.path.join(tempfile.gettempdir(), f"rcs_amd_{robot}", "scene.xml")
+    path = os.path.join(scratch_dir(), f"rcs_amd_{robot}", "scene.xml")
     if not os.path.exists(path):
         os.makedirs(os.path.dirname(path), exist_ok=True)
         xml = open(src).read()

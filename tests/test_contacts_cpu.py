@@ -88,9 +88,9 @@ def _pick_sim(density=None):
 
     path = PICKUP
     if density is not None:
-        import tempfile
+        import parity_util as pu
 
-        d = os.path.join(tempfile.gettempdir(), f"rcs_amd_pick_density_{density}")
+        d = os.path.join(pu.scratch_dir(), f"rcs_amd_pick_density_{density}")
         os.makedirs(d, exist_ok=True)
         xml = open(PICKUP).read()
         assert 'density="50"' in xml and '../fr3_empty_world/scene.xml' in xml

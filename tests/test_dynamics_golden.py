@@ -133,9 +133,8 @@ def xarm7_pick_frictionless_scene() -> str:
     """scenes/xarm7_pick_world with frictionloss = 0 on the arm joints (temporary file): the substep is then the smooth system
     plus the fingers' equality row, which the first-principles vectors predict."""
     import shutil
-    import tempfile
 
-    path = os.path.join(tempfile.gettempdir(), "rcs_amd_xarm7_pick_frictionless", "scene.xml")
+    path = os.path.join(P.scratch_dir(), "rcs_amd_xarm7_pick_frictionless", "scene.xml")
     if not os.path.exists(path):
         os.makedirs(os.path.dirname(path), exist_ok=True)
         xml = open(P.XARM7_PICK_SCENE).read()

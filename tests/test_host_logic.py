@@ -3,6 +3,7 @@
 import ctypes as C
 import os
 import re
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -12,7 +13,15 @@ from parity_util import ROOT, SCENE
 from rcs_amd import _lib, common
 from rcs_amd.mjcf import MjcfError, compile_mjcf
 
-REF_SCENE = "/root/reference/assets/scenes/fr3_empty_world/scene.xml"
+
+def _reference_scene(scene):
+    """The reference's own scene `scene`, as rcs_amd/mjcf.py compiles it: its tables, names and free body, stored in
+    tests/golden/reference_scene_tables.npz by tools/make_reference_scene_tables.py."""
+    z = np.load(os.path.join(ROOT, "tests", "golden", "reference_scene_tables.npz"))
+    part = lambda kind: {k.split("/", 2)[2]: z[k] for k in z.files if k.startswith(f"{scene}/{kind}/")}  # noqa: E731
+    fb = {k: (v.item() if v.ndim == 0 else v) for k, v in part("free_body").items()}
+    names = {k: v.tolist() for k, v in part("names").items()}
+    return SimpleNamespace(arrays=part("arrays"), free_bodies=[fb] if fb else [], **names)
 
 
 @pytest.fixture(scope="module")
@@ -55,11 +64,10 @@ def test_scene_constants_match_appendix_a(cm):
     assert np.allclose(j["body_quat"][4], np.array([1, -1, 0, 0]) / np.sqrt(2))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SCENE), reason="reference checkout not present (GPU box)")
 def test_own_scene_equals_reference_scene_tables():
     """The repository's physics-only scene compiles to the same tables as the reference's MJCF (include, default
     classes, childclass, actuator-default inheritance), except the one documented approximation (d435i_0 inertia)."""
-    own, ref = compile_mjcf(SCENE), compile_mjcf(REF_SCENE)
+    own, ref = compile_mjcf(SCENE), _reference_scene("fr3_empty_world")
     skip_rows = {"body_ipos": [11], "body_mass": [11], "body_inertia": [11], "body_iquat": [11]}
     for key, a in own.arrays.items():
         if key.startswith(("geom_", "cam_", "mesh_")):
@@ -75,7 +83,6 @@ def test_own_scene_equals_reference_scene_tables():
 
 
 XARM7_SCENE = os.path.join(os.path.dirname(SCENE), "..", "xarm7_empty_world", "scene.xml")
-REF_XARM7_SCENE = "/root/reference/assets/scenes/xarm7_empty_world/scene.xml"
 
 
 def test_xarm7_scene_constants():
@@ -94,9 +101,8 @@ def test_xarm7_scene_constants():
     assert cm.jnt_names == [f"joint{i}" for i in range(1, 8)] and cm.actuator_names == [f"act{i}" for i in range(1, 8)]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_XARM7_SCENE), reason="reference checkout not present (GPU box)")
 def test_own_xarm7_scene_equals_reference_scene_tables():
-    own, ref = compile_mjcf(XARM7_SCENE), compile_mjcf(REF_XARM7_SCENE)
+    own, ref = compile_mjcf(XARM7_SCENE), _reference_scene("xarm7_empty_world")
     for key, a in own.arrays.items():
         if key.startswith(("geom_", "cam_", "mesh_")):
             continue
@@ -244,7 +250,6 @@ def test_config_mirrors_reference_defaults():
 
 # ---------------------------------------------------------------- fr3_simple_pick_up: the free box and the task layer
 PICKUP_SCENE = os.path.join(os.path.dirname(SCENE), "..", "fr3_simple_pick_up", "scene.xml")
-REF_PICKUP_SCENE = "/root/reference/assets/scenes/fr3_simple_pick_up/scene.xml"
 
 
 def test_pick_up_scene_free_box_constants():
@@ -266,9 +271,8 @@ def test_pick_up_scene_free_box_constants():
     assert d.cone_elliptic == 1 and d.noslip_iterations == 5 and d.impratio == 20.0 and _lib.make_free_box_desc(empty) is None
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PICKUP_SCENE), reason="reference checkout not present (GPU box)")
 def test_own_pick_up_scene_equals_reference_scene():
-    own, ref = compile_mjcf(PICKUP_SCENE), compile_mjcf(REF_PICKUP_SCENE)
+    own, ref = compile_mjcf(PICKUP_SCENE), _reference_scene("fr3_simple_pick_up")
     (a,), (b,) = own.free_bodies, ref.free_bodies
     assert a.keys() == b.keys()
     for k in a:
@@ -482,7 +486,7 @@ def test_pybind_module_matches_the_reference_api():
     """The compiled binding `rcs_hip._core.sim` (extensions/rcs_hip) against the NAMES of the reference's `rcs._core.sim`
     (tests/golden/core_sim_api.json, generated from the reference's stub files by tools/make_core_api_fixture.py): every
     class, every method with its argument names, every field -- including what SimRobot / SimGripper inherit from
-    common.Robot / common.Gripper.  No GPU here: constructing a Sim must fail with the reference's exception type."""
+    common.Robot / common.Gripper.  Without a GPU, constructing a Sim must fail with the reference's exception type."""
     import json
     import re
     import sys
@@ -523,8 +527,12 @@ def test_pybind_module_matches_the_reference_api():
     from rcs_amd.mjcf import compile_mjcf
 
     cm = compile_mjcf(os.path.join(ROOT, "robot-control-stack_amd", "rcs_amd", "scenes", "fr3_empty_world", "scene.xml"))
-    with pytest.raises(RuntimeError):
-        _core.sim.Sim(rcs_hip.model_tables(cm), 4)
+    if _lib.load().rcsh_device_count() == 0:
+        with pytest.raises(RuntimeError):
+            _core.sim.Sim(rcs_hip.model_tables(cm), 4)
+    else:  # (the suite also runs on a GPU box: there the same call must build a working Sim with the reference's defaults)
+        c = _core.sim.Sim(rcs_hip.model_tables(cm), 4).get_config()
+        assert (c.async_control, c.realtime, c.frequency, c.max_convergence_steps) == (False, False, 30, 500)
     c = _core.sim.SimRobotConfig()
     c.add_id("0")
     assert c.joints[0] == "fr3_joint1_0" and c.attachment_site == "attachment_site_0" and c.base == "base_0"
