@@ -229,6 +229,40 @@ int rcsh_ik_inverse(rcsh_sim* sim, const double* pose, const double* q0, const d
                     uint8_t* success, int32_t* iterations);
 int rcsh_ik_forward(rcsh_sim* sim, const double* q0, const double* tcp_offset7, double* pose);
 
+/* ---- collision queries on caller-supplied configurations (no reference method: MjORobot.check_collision of the reference's
+ * OMPL layer, python/rcs/ompl/mj_ompl.py, writes q into mjData, runs mj_fwdPosition + mj_collision and looks at the contacts).
+ * Evaluated against the handle's scene -- the floor plane, the robot's own collision geoms (its world-welded base included) and,
+ * in a scene with a free body, that body at the pose `free_qpos` [M][7] (x y z qw qx qy qz; NULL: the body is not tested) -- and
+ * independent of n_envs: they read and write NO per-environment state, and run on the handle's stream.
+ * q rows are [M][nl]: the robot chain's joints including the finger slides (the width rcsh_ik_inverse returns).  `kinds`: bit 0
+ * robot geom <-> floor, bit 1 robot geom <-> robot geom (MuJoCo's pair filters), bit 2 robot geom <-> free body.  A pair is in
+ * contact when it penetrates by more than 1e-9 m; joint limits are not collisions (q outside the range is evaluated as given).
+ * Robots without collision geometry (the ur5e, so101 and arm6 scenes) answer "no contact" for every row.  RCSH_ERR_MODEL: the
+ * scene has geoms or geom pairs beyond the contact tables' capacity (rcsh_sim_contact_table_dropped,
+ * rcsh_sim_contact_check_unchecked_pairs), so the answer could not be exact.  RCSH_ERR_ARG: M < 0, an unknown kinds bit, a null
+ * pointer where M > 0, free_qpos in a scene without a free body, a non-finite entry (host forms only: the _dev forms do not read
+ * the values on the host), resolution <= 0.  M = 0 does nothing.
+ * Point query: hit [M] (any selected kind in contact), kinds_hit [M] (the kinds found, complete; may be NULL), pair [M][2] (MuJoCo
+ * geom ids of one penetrating pair, in MuJoCo's order within a contact, the same from run to run; -1 -1 for none; may be NULL). */
+int rcsh_collision_query(rcsh_sim* sim, const double* q, const double* free_qpos, int32_t m, int32_t kinds, uint8_t* hit,
+                         uint8_t* kinds_hit, int32_t* pair);
+int rcsh_collision_query_dev(rcsh_sim* sim, const double* q_dev, const double* free_qpos_dev, int32_t m, int32_t kinds, uint8_t* hit_dev,
+                             uint8_t* kinds_hit_dev, int32_t* pair_dev);
+/* Motion query: the straight joint-space segment q(s) = q_from + s (q_to - q_from), s in [0, 1], per row.  result [M]: 0 free -- no
+ * configuration of the segment is in contact, PROVEN by the lever certificate (never inferred from samples); 1 contact -- t_contact
+ * [M] is the smallest sampled s whose configuration the point query reports in contact; 2 undecided -- every piece that could not
+ * be certified was bisected down to `resolution` (its largest joint travel, rad or m) and no sampled point was in contact.
+ * t_contact is -1 where result != 1.  One launch per call.  The work per row is bounded whatever the resolution: after 2048
+ * evaluated configurations without a contact a row samples s = k / 32 beyond what it settled and reports 1 at the first contact,
+ * else 2 (a contact lasting over 1/32 of the segment is never reported as 2; a row that runs out after a contact reports it, though
+ * an earlier one may have gone unsampled).  A row whose finger slides leave qpos0 -+ the stroke the levers were built for is never
+ * reported 0.  A free-body quaternion of zero norm is the identity (as mju_normalize4 makes it); a scene with a colliding geom of a
+ * type other than plane, capsule, box or mesh is refused (RCSH_ERR_MODEL). */
+int rcsh_motion_query(rcsh_sim* sim, const double* q_from, const double* q_to, const double* free_qpos, int32_t m, int32_t kinds,
+                      double resolution, int32_t* result, double* t_contact);
+int rcsh_motion_query_dev(rcsh_sim* sim, const double* q_from_dev, const double* q_to_dev, const double* free_qpos_dev, int32_t m,
+                          int32_t kinds, double resolution, int32_t* result_dev, double* t_contact_dev);
+
 /* SimGripper(sim, cfg) -- rcs.cpp:508-515, SimGripper.cpp:13-39 */
 int rcsh_sim_add_gripper(rcsh_sim* sim, const rcsh_gripper_desc* gripper);
 /* Gripper.set_normalized_width -- rcs.cpp:383-384, SimGripper.cpp:79-92 (RCSH_ERR_ARG outside [0,1] / force<0) */

@@ -16,6 +16,7 @@
 #include "model_host.h"
 #include "sim_kernels.h"
 #include "render.h"
+#include "query_team.h"
 
 using namespace rcsh;
 
@@ -75,6 +76,8 @@ struct rcsh_sim {
   float link_lever[12 * 12 + 12 * 32] = {0};  // contact_types.h: CheckTable::lev ([joint][link]), then the same per GEOM ([joint][geom], kLevGeom)
   float* d_lev = nullptr;
   float* d_slack = nullptr;          // [n][kSlackStride]: the self-contact stage's remaining gaps per pair + the joints it saw last (CheckTable::slack)
+  void* d_query = nullptr;           // staging of the host-pointer collision queries (rcsh_collision_query / rcsh_motion_query), grown on demand
+  size_t query_cap = 0;
   int chk_unchecked = 0;             // admitted geom pairs past kMaxCheckPairs: neither checked at the end of a launch nor resolved as self contacts
   // per-environment escalation (sim_kernels.h: RunOp::esc_role): a step is the lean launch over the environments not in contact plus
   // the contact-resolving launch over the others
@@ -993,6 +996,7 @@ void rcsh_sim_destroy(rcsh_sim* s) {
   hipFree(s->d_model); hipFree(s->d_coll_xyzr); hipFree(s->d_coll_cls); hipFree(s->S); hipFree(s->flags); hipFree(s->conv);
   hipFree(s->d_cgeoms); hipFree(s->d_cverts); hipFree(s->d_pairs); hipFree(s->d_chk_geoms); hipFree(s->d_chk_ent); hipFree(s->d_lev);
   hipFree(s->d_slack);
+  hipFree(s->d_query);
   if (s->esc_stream) { hipStreamSynchronize(s->esc_stream); hipStreamDestroy(s->esc_stream); }
   if (s->esc_ev_prev) hipEventDestroy(s->esc_ev_prev);
   if (s->esc_ev_old) hipEventDestroy(s->esc_ev_old);
@@ -1329,6 +1333,179 @@ int rcsh_ik_forward(rcsh_sim* s, const double* q0, const double* tcp7, double* p
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!q0 || !pose) return fail(RCSH_ERR_ARG, "null argument");
   return run_ik(s, nullptr, q0, tcp7, pose, 7, nullptr, nullptr, 1);
+}
+
+// ---- collision queries on caller-supplied configurations (csrc/query_team.h)
+namespace {
+int query_check(rcsh_sim* s, int32_t m, int32_t kinds, const double* free_qpos) {
+  if (m < 0) return fail(RCSH_ERR_ARG, "negative query count");
+  if (kinds & ~kQueryKinds) return fail(RCSH_ERR_ARG, "unknown bit in the kinds mask (bit 0 floor, 1 self, 2 free body)");
+  if (free_qpos && !s->box.present) return fail(RCSH_ERR_ARG, "free_qpos given in a scene without a free body");
+  if (!s->cgeoms_dropped.empty()) return fail(RCSH_ERR_MODEL, "collision geoms beyond the contact table's capacity: the answer could not be exact");
+  if (s->chk_unchecked > 0) return fail(RCSH_ERR_MODEL, "admitted geom pairs beyond the check's table: the answer could not be exact");
+  for (int g = 0; g < s->hm.ngeom; ++g) {
+    // (the contact table holds capsules, boxes and convex meshes; a colliding geom of another type would be left out silently)
+    const int ty = s->hm.geom_type[g];
+    if (ty != 0 && ty != 3 && ty != 6 && ty != 7 && (s->hm.geom_contype[g] || s->hm.geom_conaffinity[g]))
+      return fail(RCSH_ERR_MODEL, "the scene has a colliding geom of a type the collision queries do not test (mjtGeom " + std::to_string(ty) + ")");
+  }
+  return RCSH_OK;
+}
+int query_finite(const double* a, size_t n, const char* what) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(a[i])) return fail(RCSH_ERR_ARG, std::string("non-finite entry in ") + what);
+  return RCSH_OK;
+}
+QueryArgs query_args(rcsh_sim* s, int32_t m, int32_t kinds) {
+  const Params P = make_params(s);
+  QueryArgs A{};
+  A.links = reinterpret_cast<const LinkRec*>(reinterpret_cast<const char*>(s->d_model) + sizeof(DevModel));
+  A.ck = P.chk;
+  A.ck.slack = nullptr;
+  A.ck.pad = 0;
+  A.geoms = s->d_cgeoms;
+  A.verts = s->d_cverts;
+  for (int k = 0; k < 3; ++k) A.plane_n[k] = s->cp.plane_n[k];
+  A.plane_d = s->cp.plane_d;
+  A.has_plane = s->cp.has_plane ? 1 : 0;
+  A.plane_geom = s->cp.has_plane ? s->cp.plane_geom : -1;
+  A.box_geom = s->box.present ? s->hm.ngeom : -1;  // (the free body's geom: the scene's last, split off its articulated tables)
+  A.box_ok = 0;
+  for (size_t g = 0; g < s->cgeoms.size() && g < 32; ++g) {
+    const int gid = s->cgeoms[g].geom_id;  // MuJoCo's mask filter against the box geom (contype = conaffinity = 1)
+    if ((s->hm.geom_contype[gid] & 1) || (s->hm.geom_conaffinity[gid] & 1)) A.box_ok |= 1u << g;
+  }
+  for (int k = 0; k < 3; ++k) A.box_size[k] = s->box.size[k];
+  for (int L = 0; L < 12; ++L) {
+    // (build_self_levers: a slide's lever holds over qpos0 -+ its stroke)
+    const bool slide = L < s->nl && s->dm.jtype[L] == kSlide;
+    const double stroke = slide ? std::max(std::fabs(s->dm.range[L][0] - s->dm.qpos0[L]), std::fabs(s->dm.range[L][1] - s->dm.qpos0[L])) : HUGE_VAL;
+    A.slide_lo[L] = slide ? s->dm.qpos0[L] - stroke : -HUGE_VAL;
+    A.slide_hi[L] = slide ? s->dm.qpos0[L] + stroke : HUGE_VAL;
+  }
+  A.m = m;
+  A.kinds = kinds;
+  return A;
+}
+int query_launch(rcsh_sim* s, const QueryArgs& A, bool motion) {
+  hipError_t err = hipSuccess;
+  const bool ok = dispatch_topology(s->narm, s->grip, [&](auto topo) {
+    using T = decltype(topo);
+    const dim3 grid((A.m + 3) / 4), block(64);
+    if (motion) hipLaunchKernelGGL(k_motion_query<T>, grid, block, 0, s->stream, A);
+    else hipLaunchKernelGGL(k_collision_query<T>, grid, block, 0, s->stream, A);
+    err = hipGetLastError();
+  });
+  if (!ok) return fail(RCSH_ERR_MODEL, "no kernel instantiated for this archetype");
+  if (err != hipSuccess) return fail(RCSH_ERR_DEVICE, std::string("collision query launch: ") + hipGetErrorString(err));
+  return RCSH_OK;
+}
+// device pointers in: the answer for a robot without collision geometry is written without a kernel
+int point_query_dev(rcsh_sim* s, const double* q, const double* free_qpos, int32_t m, int32_t kinds, uint8_t* hit, uint8_t* kinds_hit,
+                    int32_t* pair) {
+  if (s->cgeoms.empty()) {
+    HIP_TRY(hipMemsetAsync(hit, 0, m, s->stream));
+    if (kinds_hit) HIP_TRY(hipMemsetAsync(kinds_hit, 0, m, s->stream));
+    if (pair) HIP_TRY(hipMemsetAsync(pair, 0xff, sizeof(int32_t) * 2 * (size_t)m, s->stream));
+    return RCSH_OK;
+  }
+  QueryArgs A = query_args(s, m, kinds);
+  A.q0 = q; A.free_qpos = free_qpos; A.hit = hit; A.kinds_hit = kinds_hit; A.pair = pair;
+  return query_launch(s, A, false);
+}
+__global__ void k_query_fill(int32_t* result, double* t_contact, int m) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m) { result[i] = 0; t_contact[i] = -1.0; }
+}
+int motion_query_dev(rcsh_sim* s, const double* q_from, const double* q_to, const double* free_qpos, int32_t m, int32_t kinds, double resolution,
+                     int32_t* result, double* t_contact) {
+  if (s->cgeoms.empty()) {
+    hipLaunchKernelGGL(k_query_fill, dim3((m + 63) / 64), dim3(64), 0, s->stream, result, t_contact, m);
+    HIP_TRY(hipGetLastError());
+    return RCSH_OK;
+  }
+  QueryArgs A = query_args(s, m, kinds);
+  A.q0 = q_from; A.q1 = q_to; A.free_qpos = free_qpos; A.resolution = resolution; A.result = result; A.t_contact = t_contact;
+  return query_launch(s, A, true);
+}
+int query_stage(rcsh_sim* s, size_t bytes) {
+  if (bytes <= s->query_cap) return RCSH_OK;
+  if (s->d_query) { HIP_TRY(hipStreamSynchronize(s->stream)); HIP_TRY(hipFree(s->d_query)); s->d_query = nullptr; s->query_cap = 0; }
+  HIP_TRY(hipMalloc(&s->d_query, bytes));
+  s->query_cap = bytes;
+  return RCSH_OK;
+}
+size_t align8(size_t x) { return (x + 7) & ~(size_t)7; }
+}  // namespace
+
+int rcsh_collision_query(rcsh_sim* s, const double* q, const double* free_qpos, int32_t m, int32_t kinds, uint8_t* hit, uint8_t* kinds_hit,
+                         int32_t* pair) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  int rc = query_check(s, m, kinds, free_qpos);
+  if (rc) return rc;
+  if (m == 0) return RCSH_OK;
+  if (!q || !hit) return fail(RCSH_ERR_ARG, "null argument");
+  const size_t nl = (size_t)s->nl, n = (size_t)m;
+  if ((rc = query_finite(q, n * nl, "q"))) return rc;
+  if (free_qpos && (rc = query_finite(free_qpos, n * 7, "free_qpos"))) return rc;
+  const size_t oq = 0, of = oq + 8 * n * nl, oh = of + (free_qpos ? 8 * n * 7 : 0), ok = align8(oh + n), op = align8(ok + n), end = op + 8 * n;
+  if ((rc = query_stage(s, end))) return rc;
+  char* d = static_cast<char*>(s->d_query);
+  HIP_TRY(hipMemcpyAsync(d + oq, q, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
+  if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
+  rc = point_query_dev(s, reinterpret_cast<const double*>(d + oq), free_qpos ? reinterpret_cast<const double*>(d + of) : nullptr, m, kinds,
+                       reinterpret_cast<uint8_t*>(d + oh), reinterpret_cast<uint8_t*>(d + ok), reinterpret_cast<int32_t*>(d + op));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(hit, d + oh, n, hipMemcpyDeviceToHost, s->stream));
+  if (kinds_hit) HIP_TRY(hipMemcpyAsync(kinds_hit, d + ok, n, hipMemcpyDeviceToHost, s->stream));
+  if (pair) HIP_TRY(hipMemcpyAsync(pair, d + op, 8 * n, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RCSH_OK;
+}
+int rcsh_collision_query_dev(rcsh_sim* s, const double* q_dev, const double* free_qpos_dev, int32_t m, int32_t kinds, uint8_t* hit_dev,
+                             uint8_t* kinds_hit_dev, int32_t* pair_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  int rc = query_check(s, m, kinds, free_qpos_dev);
+  if (rc) return rc;
+  if (m == 0) return RCSH_OK;
+  if (!q_dev || !hit_dev) return fail(RCSH_ERR_ARG, "null argument");
+  return point_query_dev(s, q_dev, free_qpos_dev, m, kinds, hit_dev, kinds_hit_dev, pair_dev);
+}
+int rcsh_motion_query(rcsh_sim* s, const double* q_from, const double* q_to, const double* free_qpos, int32_t m, int32_t kinds, double resolution,
+                      int32_t* result, double* t_contact) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  int rc = query_check(s, m, kinds, free_qpos);
+  if (rc) return rc;
+  if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(RCSH_ERR_ARG, "resolution must be positive and finite");
+  if (m == 0) return RCSH_OK;
+  if (!q_from || !q_to || !result || !t_contact) return fail(RCSH_ERR_ARG, "null argument");
+  const size_t nl = (size_t)s->nl, n = (size_t)m;
+  if ((rc = query_finite(q_from, n * nl, "q_from")) || (rc = query_finite(q_to, n * nl, "q_to"))) return rc;
+  if (free_qpos && (rc = query_finite(free_qpos, n * 7, "free_qpos"))) return rc;
+  const size_t oa = 0, ob = oa + 8 * n * nl, of = ob + 8 * n * nl, orr = of + (free_qpos ? 8 * n * 7 : 0), ot = orr + 8 * n, end = ot + 8 * n;
+  if ((rc = query_stage(s, end))) return rc;
+  char* d = static_cast<char*>(s->d_query);
+  HIP_TRY(hipMemcpyAsync(d + oa, q_from, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(d + ob, q_to, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
+  if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
+  rc = motion_query_dev(s, reinterpret_cast<const double*>(d + oa), reinterpret_cast<const double*>(d + ob),
+                        free_qpos ? reinterpret_cast<const double*>(d + of) : nullptr, m, kinds, resolution, reinterpret_cast<int32_t*>(d + orr),
+                        reinterpret_cast<double*>(d + ot));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(result, d + orr, 4 * n, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(t_contact, d + ot, 8 * n, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RCSH_OK;
+}
+int rcsh_motion_query_dev(rcsh_sim* s, const double* q_from_dev, const double* q_to_dev, const double* free_qpos_dev, int32_t m, int32_t kinds,
+                          double resolution, int32_t* result_dev, double* t_contact_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  int rc = query_check(s, m, kinds, free_qpos_dev);
+  if (rc) return rc;
+  if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(RCSH_ERR_ARG, "resolution must be positive and finite");
+  if (m == 0) return RCSH_OK;
+  if (!q_from_dev || !q_to_dev || !result_dev || !t_contact_dev) return fail(RCSH_ERR_ARG, "null argument");
+  return motion_query_dev(s, q_from_dev, q_to_dev, free_qpos_dev, m, kinds, resolution, result_dev, t_contact_dev);
 }
 
 int rcsh_robot_get_state(rcsh_sim* s, uint8_t* ik_success, uint8_t* collision, uint8_t* is_moving, uint8_t* is_arrived,

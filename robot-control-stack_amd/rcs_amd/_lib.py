@@ -183,6 +183,7 @@ EXPORTS = (
     "rcsh_sim_contact_unresolved",
     "rcsh_sim_set_contact_check",
     "rcsh_sim_contact_escalated",
+    "rcsh_collision_query", "rcsh_collision_query_dev", "rcsh_motion_query", "rcsh_motion_query_dev",
 )
 
 _lib = None
@@ -259,6 +260,10 @@ def load() -> C.CDLL:
     L.rcsh_debug_dump_model.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rcsh_dev_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.rcsh_dev_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    for fn in (L.rcsh_collision_query, L.rcsh_collision_query_dev):
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    for fn in (L.rcsh_motion_query, L.rcsh_motion_query_dev):
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

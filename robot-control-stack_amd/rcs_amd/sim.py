@@ -478,6 +478,83 @@ class SimRobot:
     def set_joints_hard(self, q, mask=None) -> None:
         _lib.check(self._L.rcsh_robot_set_joints_hard(self.sim._h, _lib.ptr(self._q(q)), _lib.ptr(_mask(mask, self.n_envs))))
 
+    # kinds of contact the collision queries look at (bit masks of `kinds`)
+    COLLISION_FLOOR, COLLISION_SELF, COLLISION_FREE_BODY = 1, 2, 4
+    COLLISION_ALL = 7
+
+    def _query_rows(self, q, finger_qpos, what: str) -> np.ndarray:
+        """[M, nl] rows of the chain's joints (finger slides included) from [M, nl], or from [M, narm] plus finger_qpos."""
+        nl = int(self.sim.model.nq)
+        q = np.asarray(q, dtype=np.float64)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2:
+            raise ValueError(f"{what}: expected [M, {nl}] or [M, {self.dof}] rows")
+        if q.shape[1] == nl:
+            if finger_qpos is not None:
+                raise ValueError(f"{what}: finger_qpos given with full [M, {nl}] rows")
+            return np.ascontiguousarray(q)
+        if q.shape[1] != self.dof or nl == self.dof:
+            raise ValueError(f"{what}: expected [M, {nl}] or [M, {self.dof}] rows, got {q.shape}")
+        if finger_qpos is None:
+            raise ValueError(f"{what}: [M, {self.dof}] rows need finger_qpos")
+        f = np.broadcast_to(np.asarray(finger_qpos, dtype=np.float64).reshape(-1), (q.shape[0],))
+        out = np.empty((q.shape[0], nl))
+        out[:, : self.dof] = q
+        out[:, self.dof:] = f[:, None]  # (both slides)
+        return out
+
+    def _free_rows(self, free_qpos, m: int):
+        if free_qpos is None:
+            return None
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(free_qpos, dtype=np.float64), (m, 7)))
+
+    def check_collision(self, q, free_qpos=None, kinds: int = COLLISION_ALL, finger_qpos=None):
+        """Is the robot in collision at each configuration?  Restates ``MjORobot.check_collision(qpos)`` of the reference's OMPL
+        layer (python/rcs/ompl/mj_ompl.py): write q, mj_fwdPosition + mj_collision, report a contact of a robot geom with the floor,
+        another robot geom or an obstacle -- for M configurations at once, on the GPU, without touching any environment's state.
+
+        q: [M, nl] (the chain's joints with the finger slides, as ``get_ik().inverse`` returns them) or [M, narm] plus
+        ``finger_qpos`` (scalar or [M], applied to both slides).  free_qpos: [M, 7] (or [7]) pose of the scene's free body
+        (x y z qw qx qy qz); None: the body is not tested.  kinds: bits COLLISION_FLOOR | COLLISION_SELF | COLLISION_FREE_BODY.
+        A pair counts when it penetrates by more than 1e-9 m; joint limits are not collisions.  Robots without collision geometry
+        answer False everywhere.
+
+        Returns (hit [M] bool, kinds_hit [M] uint8 -- every kind found in contact --, pair [M, 2] int32: MuJoCo geom ids of one
+        penetrating pair, -1 -1 for none)."""
+        rows = self._query_rows(q, finger_qpos, "q")
+        m = rows.shape[0]
+        fq = self._free_rows(free_qpos, m)
+        hit = np.zeros(m, dtype=np.uint8)
+        kh = np.zeros(m, dtype=np.uint8)
+        pair = np.full((m, 2), -1, dtype=np.int32)
+        _lib.check(self._L.rcsh_collision_query(self.sim._h, _lib.ptr(rows), _lib.ptr(fq), m, int(kinds), _lib.ptr(hit), _lib.ptr(kh),
+                                                _lib.ptr(pair)))
+        return hit.astype(bool), kh, pair
+
+    def check_motion(self, q_from, q_to, resolution: float = 1e-3, free_qpos=None, kinds: int = COLLISION_ALL, finger_qpos=None):
+        """The motion validator of a sampling-based planner, for M straight joint-space segments q_from -> q_to at once (the reference
+        has ``MjORobot.check_collision`` on single configurations only; a planner samples the motion with it).
+
+        Arguments as ``check_collision``; ``resolution``: the largest joint travel (rad or m) of a piece of the segment that is left
+        undecided.  Returns (result [M] int32, t_contact [M] float64): 0 -- no configuration of the segment is in contact, proven
+        by a certificate (the links' levers against gaps measured at the ends of pieces), not by sampling; 1 -- in contact at
+        segment parameter t_contact in [0, 1] (the first sampled contact); 2 -- undecided: pieces no longer than `resolution`
+        could not be certified and no sample was in contact.  t_contact is -1 where result != 1.  The work per row is bounded
+        (include/rcs_hip.h, rcsh_motion_query): a row that spends its budget samples a grid of 1/32 of the segment, so a contact
+        lasting longer than that is never reported as 2.  Rows whose finger slides leave the stroke the levers hold for are never 0."""
+        a = self._query_rows(q_from, finger_qpos, "q_from")
+        b = self._query_rows(q_to, finger_qpos, "q_to")
+        if a.shape != b.shape:
+            raise ValueError(f"q_from {a.shape} and q_to {b.shape} differ")
+        m = a.shape[0]
+        fq = self._free_rows(free_qpos, m)
+        res = np.zeros(m, dtype=np.int32)
+        tc = np.full(m, -1.0)
+        _lib.check(self._L.rcsh_motion_query(self.sim._h, _lib.ptr(a), _lib.ptr(b), _lib.ptr(fq), m, int(kinds), float(resolution),
+                                             _lib.ptr(res), _lib.ptr(tc)))
+        return res, tc
+
 
 @dataclass
 class SimGripperConfig:  # reference src/sim/SimGripper.h:15-45
