@@ -335,6 +335,10 @@ int rcsh_sim_set_contact_options(rcsh_sim* sim, const rcsh_contact_options* opti
  * `now`: the environment is stepped by the contact-resolving kernel at present; `ever`: a contact of its robot geoms has been
  * resolved since its last rcsh_sim_reset.  All zero where escalation is off. */
 int rcsh_sim_contact_escalated(rcsh_sim* sim, uint8_t* now, uint8_t* ever);
+/* [N] flags: a contact phase of the environment ran out of contact or link slots since its last rcsh_sim_reset (the tail of MuJoCo's
+ * contact order was dropped, so from that substep on the trajectory is not the reference's); the same bit is byte 6 of an env-step's
+ * info row. */
+int rcsh_sim_contact_overflow(rcsh_sim* sim, uint8_t* overflow);
 /* [N] flags: the environment's geoms were found in a contact this configuration does not resolve -- robot <-> floor in scenes
  * that only detect contacts (the default without a free body), robot <-> robot everywhere -- at the end of a stepping launch,
  * since its last rcsh_sim_reset.  MuJoCo resolves every contact of d->contact in every mj_step2 (reference src/sim/sim.cpp:

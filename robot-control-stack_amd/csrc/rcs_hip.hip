@@ -250,7 +250,10 @@ Params make_params(rcsh_sim* s) {
   P.chk.ngeom = (int)s->cgeoms.size();
   P.chk.plane_points = P.coll.has_plane ? 1 : 0;
   P.chk.pad = 0;
-  if (const char* dm = std::getenv("RCSH_CHECK_SKIP")) P.chk.pad = std::atoi(dm);  // development: bit 0 no narrow phase, 1 no boxes, 2 no spheres
+  if (const char* dm = std::getenv("RCSH_CHECK_SKIP")) P.chk.pad = std::atoi(dm);  // development: bit 0 no narrow phase, 1 no boxes, 2 no spheres, 3 no
+  // Gilbert fallback, 4 no slack record (timing experiments, check_team.h); bit 5 sends every coupled environment of a box-less scene to the
+  // wide solve (contact_wide.h) whatever its contact count, not only those with more than kDenseCon contacts (contact_dense.h; the tests
+  // of the wide solve's math on few contacts, tests/test_gpu_contact_wide.py).  Read on every launch.
   std::memset(P.chk.gh, 0, sizeof(P.chk.gh));
   std::memset(P.chk.gvert, 0, sizeof(P.chk.gvert));
   std::memset(P.chk.glink, 0, sizeof(P.chk.glink));
@@ -1774,6 +1777,10 @@ int rcsh_sim_contact_unresolved(rcsh_sim* s, uint8_t* unresolved) {
     if (int rc = launch_run(s, op, false)) return rc;
   }
   return flag_host(s, kContactUnresolved, unresolved);
+}
+int rcsh_sim_contact_overflow(rcsh_sim* s, uint8_t* overflow) {
+  REQUIRE_SIM(s);
+  return flag_host(s, kContactOverflow, overflow);
 }
 int rcsh_sim_contact_escalated(rcsh_sim* s, uint8_t* now, uint8_t* ever) {
   REQUIRE_SIM(s);

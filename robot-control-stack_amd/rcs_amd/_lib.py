@@ -183,6 +183,7 @@ EXPORTS = (
     "rcsh_sim_contact_unresolved",
     "rcsh_sim_set_contact_check",
     "rcsh_sim_contact_escalated",
+    "rcsh_sim_contact_overflow",
     "rcsh_collision_query", "rcsh_collision_query_dev", "rcsh_motion_query", "rcsh_motion_query_dev",
 )
 
@@ -226,6 +227,7 @@ def load() -> C.CDLL:
     L.rcsh_sim_add_free_box.argtypes = [C.c_void_p, C.POINTER(FreeBoxDesc)]
     L.rcsh_sim_set_contact_options.argtypes = [C.c_void_p, C.POINTER(ContactOptions)]
     L.rcsh_sim_contact_escalated.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rcsh_sim_contact_overflow.argtypes = [C.c_void_p, C.c_void_p]
     L.rcsh_sim_reset_free_box.argtypes = [C.c_void_p]
     L.rcsh_sim_contact_check_unchecked_pairs.argtypes = [C.c_void_p, _I32P]
     L.rcsh_sim_contact_table_dropped.argtypes = [C.c_void_p, _I32P, C.c_int32, _I32P, C.c_char_p, C.c_size_t]

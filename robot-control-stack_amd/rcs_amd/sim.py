@@ -146,6 +146,15 @@ class Sim:
         per env-step; 0: off).  See rcsh_sim_set_contact_check (include/rcs_hip.h) for what a larger cadence trades."""
         _lib.check(self._L.rcsh_sim_set_contact_check(self._h, int(every)))
 
+    def contact_overflow(self) -> np.ndarray:
+        """[N] bool: a contact phase of the environment ran out of contact or link slots since its last Sim.reset (the tail of
+        MuJoCo's contact order was dropped; also info["contact_overflow"])."""
+        import numpy as np
+
+        out = np.zeros(self.n_envs, dtype=np.uint8)
+        _lib.check(self._L.rcsh_sim_contact_overflow(self._h, _lib.ptr(out)))
+        return out.astype(bool)
+
     def contact_unresolved(self) -> np.ndarray:
         """[N] bool: the environment's geoms were found in a contact this configuration does not resolve, since its last
         Sim.reset (the sticky flag the end-of-launch check sets, csrc/check_team.h; also info["contact_unresolved"])."""

@@ -1127,6 +1127,7 @@ def run_floor_contact_parity(n_envs=8, seed=0):
         rep["collisions"] += int(bool(o.s.robot_collision) or bool(o.s.grp_collision))
         rep["min_z"] = min(rep["min_z"], float(o.get_cartesian_position().translation()[2]))
     rep["tracking_error"] = float(np.abs(simu.qpos[:, :7] - tgt).max())
+    rep["qpos_end"], rep["qvel_end"] = np.array(simu.qpos), np.array(simu.qvel)
     simu.close()
     return rep
 
@@ -1542,7 +1543,8 @@ def run_self_contact_parity(n_envs=24, seed=1, launches=40, substeps=17, mode=7)
     rep["resolved_ever"] = ever
     rep["in_contact_at_end"] = np.array([o.s.d.ncon > 0 for o in osims])
     rep["tracking_error"] = np.abs(simu.qpos[:, :7] - q).max(axis=1)
-    rep["overflow"] = int(np.asarray(simu.contact_overflow()).sum()) if hasattr(simu, "contact_overflow") else 0
+    rep["overflow"] = int(np.asarray(simu.contact_overflow()).sum())
+    rep["qpos_end"], rep["qvel_end"] = np.array(simu.qpos), np.array(simu.qvel)
     simu.close()
     return rep
 
@@ -1664,3 +1666,231 @@ def run_headline_resolved_parity(n_envs=64, n_steps=1000, seed=0):
     rep["overflow"] = int(np.asarray(info["contact_overflow"]).sum())
     venv.close()
     return rep
+
+
+def _many_contact_oracle(cm, q, nudge=0.0):
+    """One oracle environment of the many-contact workload: resolving floor AND self contacts (resolve_contacts=3), async control,
+    the gripper at its reset width, a first substep at home, then the joint target `q` (SimRobot.set_joint_position: no clipping).
+    `nudge` is added to qpos[3] before the target is set (the twin)."""
+    import rcs_oracle as O
+    from rcs_env_oracle import FR3_Q_HOME
+
+    arm = [f"fr3_joint{i}_0" for i in range(1, 8)]
+    o = O.Sim(cm, arm, arm, "attachment_site_0", "base_0", FR3_Q_HOME, None, "finger_joint1_0", "actuator8_0", resolve_contacts=3)
+    o.s.async_control = 1
+    o.reset(); o.robot_reset(); o.gripper_reset(); o.step(1)
+    o.s.d.qpos[3] += nudge
+    o.set_joint_position(q)
+    return o
+
+
+def _oracle_contact_kinds(d):
+    """(contacts, floor contacts, self contacts, robot bodies in contact) of the oracle's last collision pass."""
+    nfloor = nself = 0
+    bodies = set()
+    for c in range(d.ncon):
+        b0, b1 = d.contact[c].body[0], d.contact[c].body[1]
+        if b0 > 0 and b1 > 0:
+            nself += 1
+        else:
+            nfloor += 1
+        bodies.update(b for b in (b0, b1) if b > 0)
+    return int(d.ncon), nfloor, nself, len(bodies)
+
+
+MANY_CONTACT_TWIN_NUDGE = 1e-13   # rad on qpos[3]: the twin of every oracle environment
+MANY_CONTACT_SPLIT = 1e-10        # the twins have parted once their joint positions differ by more than this
+MANY_CONTACT_CAP = 64             # kMaxConNoBox (csrc/contact_types.h): the contact-resolving kernel's contact slots without a free body
+MANY_CONTACT_WIDE = 21            # kDenseCon without a box (csrc/contact_dense.h): more contacts than this go to the wide solve
+MANY_CONTACT_DEEP = 48
+
+
+# Joint targets of the many-contact workload (run_many_contact_parity), written by tools/make_many_contact_targets.py: a seeded draw
+# filtered by the oracle alone (tests/test_contacts_cpu.py checks that they still reach their classes).  Each line's comment: the
+# classes it was picked for and what the oracle reported for it (`max_ncon_pre_split`: the most contacts in a substep before the twins
+# part; `wide_held` / `deep_held` / `mixed_held`: substeps with more than 21 / more than 48 contacts / floor and self contacts together,
+# in launches held to the plain bars; `split` / `over_cap`: the launch the twins part in / the oracle first passes 64 contacts in).
+MANY_CONTACT_TARGETS = np.array([
+    [0.794427601939151, 1.666778651489735, 0.0, -1.0789406184087145, 0.0, 3.214622982804322, 0.45193933917425877],  # floor: {'max_ncon_pre_split': 43, 'wide_held': 26, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [-0.5495856200188163, 1.4264019791423475, 0.0, -1.427951056912987, 0.0, 2.031992468562791, 0.8893685428365474],  # floor: {'max_ncon_pre_split': 44, 'wide_held': 45, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [-0.39966743017754913, 0.9521414452640432, 0.0, -0.2459924704436851, 0.0, 2.2468355677068614, -2.394623227780545],  # quiet: {'max_ncon_pre_split': 0, 'wide_held': 0, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [0.7471068907925238, 1.2411159849774414, 0.0, -0.6791349779460798, 0.0, 3.282251669396439, -0.9471490147340256],  # floor: {'max_ncon_pre_split': 22, 'wide_held': 7, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [-0.9894693908688506, 1.1842719847072218, 0.0, -1.0004916550547263, 0.0, 1.6023981919954196, 2.19170643432307],  # floor: {'max_ncon_pre_split': 22, 'wide_held': 23, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [0.5941388575040925, 1.6183775313607867, 0.0, -0.37806710800931587, 0.0, 2.623530879996624, 1.5579370137337536],  # floor: {'max_ncon_pre_split': 26, 'wide_held': 15, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [-0.06413009431255845, 1.233912630964275, 0.0, -1.1181050662055634, 0.0, 2.721006170274695, 0.7901304080586291],  # floor: {'max_ncon_pre_split': 42, 'wide_held': 37, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [-0.39393514636137295, 1.761298138281875, 0.0, -0.7735926247943995, 0.0, 2.511093238816488, 0.5537539280676311],  # floor: {'max_ncon_pre_split': 43, 'wide_held': 33, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [-0.44314877579845335, 1.419192689849337, 0.0, -0.6428418773246388, 0.0, 3.331745700307792, -1.5437365995755132],  # floor: {'max_ncon_pre_split': 22, 'wide_held': 11, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [-0.4902608246917508, 1.432449503370269, 0.0, -1.102420712167083, 0.0, 1.7984355021071796, 0.3719737412890298],  # floor: {'max_ncon_pre_split': 45, 'wide_held': 35, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [-0.10984738823470686, 1.4614369910937324, 0.0, -0.8732621189056139, 0.0, 1.9558613432304894, -2.301567907705],  # floor: {'max_ncon_pre_split': 42, 'wide_held': 164, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [0.5853238384275061, 1.1108162864099806, 0.0, -0.2932128507695999, 0.0, 3.19711455309738, -2.2464517701696938],  # quiet: {'max_ncon_pre_split': 0, 'wide_held': 0, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [-2.038183869324294, -0.00257615353113394, 0.588832571916146, -2.959180159102569, -1.97619088726674, 4.231725467607771, -2.5911371687531153],  # quiet: {'max_ncon_pre_split': 0, 'wide_held': 0, 'deep_held': 0, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [1.6744032309315462, -1.1052874823233172, -2.3617416925177355, -2.990184328353417, -1.1620309488611615, 3.4328786917937713, -0.041143203309240484],  # mixed: {'max_ncon_pre_split': 4, 'wide_held': 0, 'deep_held': 0, 'mixed_held': 124, 'split': -1, 'over_cap': -1}
+    [2.5659643103976237, 0.33526014700267703, 1.0059833789884265, -1.9632103248875272, -1.7785577579759064, 1.703308716674179, 1.3309561139555313],  # deep/floor: {'max_ncon_pre_split': 62, 'wide_held': 6, 'deep_held': 5, 'mixed_held': 0, 'split': -1, 'over_cap': -1}
+    [1.3493866823189626, 1.5796051133429017, 1.8653939113628497, -0.3903421974475463, -2.087767065534034, 0.6069244217150032, -1.818061549286919],  # mixed: {'max_ncon_pre_split': 21, 'wide_held': 0, 'deep_held': 0, 'mixed_held': 28, 'split': -1, 'over_cap': -1}
+    [-0.10406586262767625, 1.32382826223746, 1.255717005501881, -2.4546920566954737, -2.605401912953287, 0.8131014353474286, -0.38729973244718385],  # mixed: {'max_ncon_pre_split': 3, 'wide_held': 0, 'deep_held': 0, 'mixed_held': 31, 'split': -1, 'over_cap': -1}
+    [-2.3791674327085386, -1.0683950715906247, 2.5409556022084634, -2.9871590264606684, -1.3518584783815737, 2.110633518122632, -3.0123667315759715],  # mixed: {'max_ncon_pre_split': 4, 'wide_held': 0, 'deep_held': 0, 'mixed_held': 83, 'split': -1, 'over_cap': -1}
+    [-1.8511016054195855, -1.6983273958143816, 2.8765515517876374, -2.78049638561267, 2.1700396744748685, 2.0005316295265017, -2.5230862829491683],  # mixed: {'max_ncon_pre_split': 23, 'wide_held': 8, 'deep_held': 0, 'mixed_held': 170, 'split': -1, 'over_cap': -1}
+    [-2.6282677958438314, 1.2131672241206979, -0.24584761907340136, -1.6929987957610957, 0.7454837093660802, 3.7578719792780415, 1.2390560119421132],  # deep/over: {'max_ncon_pre_split': 65, 'wide_held': 29, 'deep_held': 0, 'mixed_held': 0, 'split': 12, 'over_cap': 12}
+    [0.8239457052697192, 1.7420584687163392, 1.4341485633239768, -2.312005490813659, -2.6491266856945774, 2.253821934896081, -0.9650810173182447],  # deep/over: {'max_ncon_pre_split': 75, 'wide_held': 0, 'deep_held': 0, 'mixed_held': 0, 'split': 8, 'over_cap': 8}
+])
+
+
+def many_contact_oracle_run(targets, launches=30, substeps=17, keep=False):
+    """The oracle side of the many-contact workload (run_many_contact_parity), environment by environment, with its twin.
+
+    Per environment (arrays of length len(targets)), with "launch" one Sim.step(substeps):
+    * `split`: the first launch after which the twins' joint positions are more than 1e-10 apart (-1: never);
+    * `over_cap`: the first launch in which some substep of the oracle has more than 64 contacts (-1: never);
+    * `twin_over_cap`: the same for the twin;
+    * `split_substep` / `over_cap_substep`: the same two events to the substep (counted from the target's first substep), -1: never;
+    * `count_split_substep`: the first substep in which the twins' collision passes report different contact counts (-1: never).  Pads
+      pressed face to face make the count depend on the last bit several substeps before the joint positions part (a target of
+      MANY_CONTACT_TARGETS: 19 contacts in the oracle, 23 in its twin, qpos 5e-14 apart; 65 against 61 four substeps later);
+    * `cap_first`: the oracle passes 64 contacts in a substep before its twins part in either sense (an overflow the kernel must
+      reproduce); `cap_before_split`: ... before their joint positions part (the contact count may already be the last bit's);
+    * `held`: the launches before min(split, over_cap) -- the ones the kernel is held to 1e-9 / 1e-8 in (`launches` when neither happens);
+    * `max_ncon_held` / `max_ncon_pre_split` / `max_ncon`: the most contacts in one substep, before `held` ends / before the substep the
+      twins part in / over the whole run (the twin's included);
+    * `wide_held` / `deep_held` / `mixed_held`: substeps before `held` ends with more than 21 contacts, more than 48, floor and self
+      contacts together;
+    * `max_bodies_held`: the most robot bodies in contact at once before `held` ends;
+    * `touched`: the oracle had a contact in some substep.
+    With `keep`, also the per-launch qpos / qvel of the oracle and the twins' distance (`qpos`, `qvel`: [E, launches, nq]; `twin_dq`,
+    `twin_dv`: [E, launches], running maxima)."""
+    from rcs_amd.envs import default_sim_robot_cfg
+    from rcs_amd.mjcf import compile_mjcf
+
+    cm = compile_mjcf(default_sim_robot_cfg("fr3_empty_world").mjcf_scene_path)
+    targets = np.asarray(targets, dtype=np.float64)
+    n = len(targets)
+    rep = {k: np.full(n, -1) for k in ("split", "over_cap", "twin_over_cap", "split_substep", "over_cap_substep", "count_split_substep")}
+    for k in ("held", "max_ncon_held", "max_ncon", "max_ncon_pre_split", "wide_held", "deep_held", "mixed_held", "max_bodies_held"):
+        rep[k] = np.zeros(n, dtype=int)
+    rep["touched"] = np.zeros(n, dtype=bool)
+    if keep:
+        rep["qpos"], rep["qvel"], rep["twin_dq"], rep["twin_dv"] = [], [], np.zeros((n, launches)), np.zeros((n, launches))
+    for e in range(n):
+        o = _many_contact_oracle(cm, targets[e])
+        tw = _many_contact_oracle(cm, targets[e], MANY_CONTACT_TWIN_NUDGE)
+        qs, vs = [], []
+        dq = dv = 0.0
+        for L in range(launches):
+            held = rep["split"][e] < 0 and rep["over_cap"][e] < 0
+            cnt = {"max_ncon_held": 0, "max_bodies_held": 0, "wide_held": 0, "deep_held": 0, "mixed_held": 0}
+            for k in range(substeps):
+                o.step(1)
+                tw.step(1)
+                ncon, nfloor, nself, nbod = _oracle_contact_kinds(o.s.d)
+                tcon = int(tw.s.d.ncon)
+                if rep["split_substep"][e] < 0 and np.abs(np.asarray(tw.qpos) - np.asarray(o.qpos)).max() > MANY_CONTACT_SPLIT:
+                    rep["split_substep"][e] = L * substeps + k
+                if rep["count_split_substep"][e] < 0 and tcon != ncon:
+                    rep["count_split_substep"][e] = L * substeps + k
+                if ncon > MANY_CONTACT_CAP and rep["over_cap_substep"][e] < 0:
+                    rep["over_cap_substep"][e] = L * substeps + k
+                if rep["split_substep"][e] < 0:
+                    rep["max_ncon_pre_split"][e] = max(rep["max_ncon_pre_split"][e], ncon)
+                rep["touched"][e] |= ncon > 0
+                rep["max_ncon"][e] = max(rep["max_ncon"][e], ncon, tcon)
+                if ncon > MANY_CONTACT_CAP and rep["over_cap"][e] < 0:
+                    rep["over_cap"][e] = L
+                if tcon > MANY_CONTACT_CAP and rep["twin_over_cap"][e] < 0:
+                    rep["twin_over_cap"][e] = L
+                cnt["max_ncon_held"] = max(cnt["max_ncon_held"], ncon)
+                cnt["max_bodies_held"] = max(cnt["max_bodies_held"], nbod)
+                cnt["wide_held"] += ncon > MANY_CONTACT_WIDE
+                cnt["deep_held"] += ncon > MANY_CONTACT_DEEP
+                cnt["mixed_held"] += nfloor > 0 and nself > 0
+            dq = max(dq, float(np.abs(np.asarray(tw.qpos) - np.asarray(o.qpos)).max()))
+            dv = max(dv, float(np.abs(np.asarray(tw.qvel) - np.asarray(o.qvel)).max()))
+            if rep["split"][e] < 0 and dq > MANY_CONTACT_SPLIT:
+                rep["split"][e] = L
+            if held and rep["over_cap"][e] < 0 and rep["split"][e] < 0:  # (a launch that ends held: its substeps count as evidence)
+                rep["held"][e] = L + 1
+                for k, c in cnt.items():
+                    rep[k][e] = max(rep[k][e], c) if k.startswith("max") else rep[k][e] + c
+            if keep:
+                qs.append(np.array(o.qpos))
+                vs.append(np.array(o.qvel))
+                rep["twin_dq"][e, L], rep["twin_dv"][e, L] = dq, dv
+        if keep:
+            rep["qpos"].append(np.array(qs))
+            rep["qvel"].append(np.array(vs))
+    if keep:
+        rep["qpos"], rep["qvel"] = np.array(rep["qpos"]), np.array(rep["qvel"])
+    big = 1 << 30
+    parted = np.minimum(np.where(rep["split_substep"] < 0, big, rep["split_substep"]), np.where(rep["count_split_substep"] < 0, big, rep["count_split_substep"]))
+    rep["cap_first"] = (rep["over_cap_substep"] >= 0) & (rep["over_cap_substep"] < parted)
+    rep["cap_before_split"] = (rep["over_cap_substep"] >= 0) & (rep["over_cap_substep"] < np.where(rep["split_substep"] < 0, big, rep["split_substep"]))
+    return rep
+
+
+def run_many_contact_parity(targets=None, launches=30, substeps=17, mode=7, oracle=None):
+    """Many contacts in a scene without a free body: the contact-resolving kernel's wide solve (csrc/contact_wide.h: a lane per contact,
+    taken by an environment with more than 21 contacts) against the oracle that resolves floor AND self contacts with no bound on its
+    contact list.  fr3_empty_world, async control, Sim.step(`substeps`) launches towards joint targets (MANY_CONTACT_TARGETS: hands driven
+    into the floor with the fingers open -- 22-44 floor contacts --, arms folded onto themselves, and both at once), kernel with
+    resolve_robot_contacts `mode` (7: environment by environment, 3: the whole batch on the contact-resolving kernel).  `oracle`: a
+    many_contact_oracle_run(..., keep=True) report of the same targets to reuse.
+
+    Every launch, every environment, the kernel's qpos / qvel against the oracle's (many_contact_oracle_run's twins say which launches a
+    bar applies to):
+    * `excess_q` / `excess_v`: the largest error in the launches before the twins part and before the oracle passes 64 contacts (the
+      caller's bars: 1e-9 / 1e-8), and in the launch the twins part in the error less 100 x the twins' distance;
+    * from the launch in which the oracle passes 64 contacts on (kMaxConNoBox: the kernel drops the tail of the contact order by design)
+      the environment is held only to its overflow flag; after the twins part, to nothing (`post_err`: reported).
+    Also: `overflow` (Sim.contact_overflow), `escalated_now` / `resolved_ever` (Sim.contact_escalated), the kernel's qpos / qvel after every
+    launch (`kq`, `kv`: [E, launches, nq]) and the oracle report (`oracle`)."""
+    from rcs_amd import sim as S
+    from rcs_amd.envs import default_sim_gripper_cfg, default_sim_robot_cfg
+
+    targets = MANY_CONTACT_TARGETS if targets is None else np.asarray(targets, dtype=np.float64)
+    n = len(targets)
+    orc = oracle if oracle is not None else many_contact_oracle_run(targets, launches, substeps, keep=True)
+    cfg = default_sim_robot_cfg("fr3_empty_world")
+    simu = S.Sim(cfg.mjcf_scene_path, S.SimConfig(async_control=True), n_envs=n, resolve_robot_contacts=mode)
+    robot = S.SimRobot(simu, None, cfg)
+    S.SimGripper(simu, default_sim_gripper_cfg())
+    simu.step(1)
+    robot.set_joint_position(targets)
+    excess_q, excess_v, post_err = np.zeros(n), np.zeros(n), np.zeros(n)
+    kq, kv = [], []
+    for L in range(launches):
+        simu.step(substeps)
+        q, v = simu.qpos, simu.qvel
+        kq.append(np.array(q))
+        kv.append(np.array(v))
+        nq = q.shape[1]
+        dq = np.abs(q - orc["qpos"][:, L, :nq]).max(axis=1)
+        dv = np.abs(v - orc["qvel"][:, L, :nq]).max(axis=1)
+        for e in range(n):
+            split, cap = orc["split"][e], orc["over_cap"][e]
+            if cap >= 0 and L >= cap:
+                continue  # (held to its overflow flag)
+            if split < 0 or L < split:
+                excess_q[e], excess_v[e] = max(excess_q[e], dq[e]), max(excess_v[e], dv[e])
+            elif L == split:
+                excess_q[e] = max(excess_q[e], dq[e] - 100.0 * orc["twin_dq"][e, L])
+                excess_v[e] = max(excess_v[e], dv[e] - 100.0 * orc["twin_dv"][e, L])
+            else:
+                post_err[e] = max(post_err[e], dq[e])
+    now, ever = simu.contact_escalated()
+    rep = {"excess_q": excess_q, "excess_v": excess_v, "post_err": post_err, "overflow": simu.contact_overflow(),
+           "escalated_now": now, "resolved_ever": ever, "kq": np.array(kq).transpose(1, 0, 2), "kv": np.array(kv).transpose(1, 0, 2),
+           "oracle": orc}
+    simu.close()
+    return rep
+
+
+def many_contact_summary(rep):
+    """The per-environment lines of a run_many_contact_parity report, for the record (profiles/contact_wide_tests.txt)."""
+    o = rep["oracle"]
+    out = ["env max_ncon_pre_split wide_held deep_held mixed_held split over_cap | excess_q excess_v overflow esc_now esc_ever"]
+    for e in range(len(rep["excess_q"])):
+        out.append(f"{e:3d} {o['max_ncon_pre_split'][e]:3d} {o['wide_held'][e]:4d} {o['deep_held'][e]:3d} {o['mixed_held'][e]:4d} "
+                   f"{o['split'][e]:3d} {o['over_cap'][e]:3d} | {rep['excess_q'][e]:.2e} {rep['excess_v'][e]:.2e} "
+                   f"{int(rep['overflow'][e])} {int(rep['escalated_now'][e])} {int(rep['resolved_ever'][e])}")
+    out.append(f"substeps held to the plain bars with > 21 contacts {int(o['wide_held'].sum())}, > 48 {int(o['deep_held'].sum())}, "
+               f"floor and self together {int(o['mixed_held'].sum())}; oracle past 64 before its twins' positions part: {int(o['cap_before_split'].sum())} environments, before their contact counts "
+               f"part too: {int(o['cap_first'].sum())}; kernel overflow flags: {int(np.asarray(rep['overflow']).sum())}")
+    return "\n".join(out)

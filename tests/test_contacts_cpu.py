@@ -552,3 +552,25 @@ def test_effective_path_bounds_every_position_a_joint_took():
         assert (np.abs(q - q0) + np.abs(q - q1) <= psum + 1e-12).all()
     q = np.linspace(0.3, -0.1, 18)  # monotone: the bound is attained, nothing is given away
     assert abs((2 * (q.max() - q.min()) - abs(q[-1] - q[0])) - abs(q[-1] - q[0])) < 1e-15
+
+
+def test_many_contact_targets_still_reach_their_classes():
+    """The targets of the wide-solve parity test (tests/test_gpu_contact_wide.py; parity_util.MANY_CONTACT_TARGETS, written by
+    tools/make_many_contact_targets.py) on the oracle alone: if the oracle changes, the GPU test must not quietly lose its many-contact
+    coverage.  Per class, from the oracle and its twin (qpos[3] nudged by 1e-13 rad), over 30 launches of 17 substeps: hands on the floor
+    with more than 21 contacts (the wide solve) and twins that never part, more than 48, floor and self contacts at once, two that pass
+    the 64 contact slots before their twins' joint positions part, and quiet ones."""
+    from parity_util import MANY_CONTACT_TARGETS, many_contact_oracle_run
+
+    r = many_contact_oracle_run(MANY_CONTACT_TARGETS)
+    floor = (r["wide_held"] > 0) & (r["mixed_held"] == 0) & (r["split"] < 0) & (r["max_ncon"] <= 64)
+    assert floor.sum() >= 10 and r["wide_held"].sum() >= 400, r
+    assert (r["max_ncon_pre_split"] > 48).sum() >= 3 and r["deep_held"].sum() >= 5, r
+    assert (r["mixed_held"] > 0).sum() >= 5 and r["mixed_held"].sum() >= 400 and ((r["mixed_held"] > 0) & (r["wide_held"] > 0)).any(), r
+    assert r["cap_before_split"].sum() >= 2, r
+    assert (~r["touched"] & (r["split"] < 0)).sum() >= 3, r
+    # only the environments that pass 64 contacts part from their twins, and none passes 64 after its twins parted (the kernel's overflow
+    # flag would then be decided by which of the two trajectories it follows)
+    assert np.array_equal(r["split"] >= 0, r["cap_before_split"]) and np.array_equal(r["max_ncon"] > 64, r["cap_before_split"]), r
+    # every launch the GPU test compares at the plain bars has at most 5 robot bodies in contact (kMaxActive, csrc/contact_types.h)
+    assert r["max_bodies_held"].max() <= 5, r
