@@ -419,6 +419,45 @@ int rcsh_env_reset_task_dev(rcsh_sim* sim, const uint8_t* mask_dev, const double
 int rcsh_env_step_task_dev(rcsh_sim* sim, const double* action_dev, const float* gripper_dev, double* obs_dev, uint8_t* info_dev,
                            double* gripper_width_dev, int32_t* substeps_dev, double* task_dev);
 
+/* Collision guard of the fused loop: the reference's CollisionGuard wrapper (python/rcs/envs/sim.py:156-287), which sits between
+ * RelativeActionSpace and RobotEnv.step, for N environments and decided on the device.  Before a guarded step one launch asks, per
+ * environment, the motion query's question about the environment's OWN segment: from its current chain configuration (arm joints
+ * and finger slides) to the absolute joint command this action would hand to RobotEnv.step (the relative action space's arithmetic,
+ * recomputed without touching what it remembers), finger slides kept, the free body -- kinds bit 2, scenes that have one -- at the
+ * environment's own current pose.  result / t_contact are the motion query's (0 free: PROVEN by the lever certificate, 1 contact,
+ * 2 undecided), with two differences that the guard's fixed finger slides allow:
+ *  - a pair of geoms none of whose separating joints travels over the segment (finger against finger, finger against hand) keeps
+ *    its relative pose and is decided by the sample at the segment's start alone -- the closed hand's pads touch at a gap of
+ *    exactly 0, which passes no certificate: the motion query reports such a row 2, the guard does not;
+ *  - a finger slide up to 0.5 mm past the stroke the levers were built for is still certified (an open finger rests on its joint
+ *    limit and the soft limit lets it through by micrometres; the levers carry a millimetre of additive slack), where the motion
+ *    query reports such a row 2.
+ * blocked = result 1, or result 2 with block_undecided.  A blocked environment steps like every other one, but RobotEnv.step
+ * receives its current joint position instead of the action's command (the relative action space advances on the original action,
+ * the gripper command applies unchanged); with `truncate` its info row reports truncated.  An environment in contact at the start
+ * of its segment is blocked (result 1, t_contact 0) until it is reset.
+ * Two deviations from the reference, on purpose: the decision is the kinematic certificate, not a shadow simulation; and a blocked
+ * environment is stepped with the hold command and observed afresh, where the reference returns its previous observation.
+ * Joint-space control only: RCSH_ERR_STATE in a Cartesian control mode (configuring, and peeking; rcsh_env_configure refuses a
+ * Cartesian mode while a guard is enabled) or before rcsh_env_configure; RCSH_ERR_ARG for kinds outside 1..7 or resolution <= 0;
+ * RCSH_ERR_MODEL where the motion query refuses the scene.  A refused call changes nothing.  The guard keeps no state that outlives
+ * a step. */
+typedef struct rcsh_guard_desc {
+  int32_t enabled;         /* 0: the steps run unguarded (rcsh_env_guard_peek still answers) */
+  int32_t kinds;           /* as rcsh_motion_query: bit 0 floor, 1 self, 2 free body (ignored in a scene without one) */
+  double resolution;       /* as rcsh_motion_query, > 0 */
+  int32_t block_undecided; /* result 2 blocks too */
+  int32_t truncate;        /* blocked environments report truncated (info row, byte 4) */
+} rcsh_guard_desc;
+int rcsh_env_configure_guard(rcsh_sim* sim, const rcsh_guard_desc* guard);
+/* The guard's decision for an action batch [N][dof], without stepping and without writing any state. */
+int rcsh_env_guard_peek(rcsh_sim* sim, const double* action, int32_t* result, double* t_contact, uint8_t* blocked);
+int rcsh_env_guard_peek_dev(rcsh_sim* sim, const double* action_dev, int32_t* result_dev, double* t_contact_dev, uint8_t* blocked_dev);
+/* The record of the most recent guarded step (RCSH_ERR_STATE: there was none): copied to the host, or as device pointers that stay
+ * valid for the handle's life and are rewritten by every guarded step. */
+int rcsh_env_guard_last(rcsh_sim* sim, int32_t* result, double* t_contact, uint8_t* blocked);
+int rcsh_env_guard_last_dev(rcsh_sim* sim, const int32_t** result_dev, const double** t_contact_dev, const uint8_t** blocked_dev);
+
 
 /* Depth images: the pixel path of SimCameraSet (reference src/sim/camera.cpp:86-140 render_single -> mjv_updateScene,
  * mjr_render, mjr_readPixels; python/rcs/camera/sim.py:45-115 for the row flip, the conversion to metres and the

@@ -386,21 +386,20 @@ __global__ void __launch_bounds__(64) k_collision_query(QueryArgs A) {
   }
 }
 
-// Motion query: one segment per team (see the top of this file).  result: 0 free (certified), 1 contact at t_contact, 2 undecided.
-template <class T>
-__global__ void __launch_bounds__(64) k_motion_query(QueryArgs A) {
-  constexpr int kTeams = 64 / kTeamLanes, NL = T::NL;
-  __shared__ QueryTeamLds<T> lds[kTeams];
-  const int team = threadIdx.x / kTeamLanes, t = threadIdx.x % kTeamLanes;
-  const int e = blockIdx.x * kTeams + team;
-  const bool live = e < A.m;
+// The motion validator of one segment per team (see the top of this file), for whoever supplies the segment: the motion query
+// (caller's rows) and the environments' collision guard (guard_team.h: the environment's own state and action).  Every lane of the
+// wavefront calls it; qa, qb: the lane's joint at the two ends (t < NL), fq / use_box: the free body as query_config takes it.
+// result: 0 free (certified), 1 contact at tc, 2 undecided; tc: -1 unless result is 1.  The same on every lane of the team.
+// kRigidPairsBySample: a pair of geoms none of whose separating joints travels over the segment keeps its relative pose, so its gap at
+// s = 0 is its gap everywhere: not penetrating there, it is free without a certificate (which a gap of exactly 0 -- the closed hand's
+// pads -- never passes).  The guard asks for it (its finger slides stand still by construction); the motion query keeps its rule.
+template <class T, bool kRigidPairsBySample = false>
+RCSH_D void motion_decide(const QueryArgs& A, QueryTeamLds<T>& S, bool live, double qa, double qb, const double* fq, bool use_box,
+                          int& result, double& t_contact) {
+  constexpr int NL = T::NL;
+  const int t = threadIdx.x % kTeamLanes;
   const int tbase = threadIdx.x & 48;
-  const double qa = live && t < NL ? A.q0[(size_t)e * NL + t] : 0.0;
-  const double qb = live && t < NL ? A.q1[(size_t)e * NL + t] : 0.0;
   const double dq = qb - qa;
-  double fq[7];
-  const bool use_box = query_free_pose(A, e, live, fq);
-  QueryTeamLds<T>& S = lds[team];
   const CheckTable& ck = A.ck;
   // how far each joint travels over the whole segment, on every lane; the largest of them
   double trav[NL], maxtrav = 0.0;
@@ -424,7 +423,9 @@ __global__ void __launch_bounds__(64) k_motion_query(QueryArgs A) {
     if (i < ck.npair) {
       const uint32_t gg = ck.ent[i].geoms;
       const int g0 = gg & 0xff, g1 = (gg >> 8) & 0xff, c = (int)((gg >> 16) & 0xff) - 1;
-      mp[j] = (reach(g0, ck.glink[g0], c) + reach(g1, ck.glink[g1], c)) * 1.000001 + 1e-12;
+      const double rel = reach(g0, ck.glink[g0], c) + reach(g1, ck.glink[g1], c);
+      // (mp = 0: the certificate skips the pair; every sampled configuration, the first one included, still tests it for contact)
+      mp[j] = kRigidPairsBySample && rel == 0.0 ? 0.0 : rel * 1.000001 + 1e-12;
     }
   }
 #pragma unroll
@@ -496,9 +497,28 @@ __global__ void __launch_bounds__(64) k_motion_query(QueryArgs A) {
       else { grid = true; gk = (int)floor(sL * kQueryGrid) + 1; if (gk > kQueryGrid) { undecided = true; done = true; } }
     }
   }
+  result = have_hit ? 1 : (undecided ? 2 : 0);
+  t_contact = have_hit ? tc : -1.0;
+}
+
+// Motion query: one segment per team.
+template <class T>
+__global__ void __launch_bounds__(64) k_motion_query(QueryArgs A) {
+  constexpr int kTeams = 64 / kTeamLanes, NL = T::NL;
+  __shared__ QueryTeamLds<T> lds[kTeams];
+  const int team = threadIdx.x / kTeamLanes, t = threadIdx.x % kTeamLanes;
+  const int e = blockIdx.x * kTeams + team;
+  const bool live = e < A.m;
+  const double qa = live && t < NL ? A.q0[(size_t)e * NL + t] : 0.0;
+  const double qb = live && t < NL ? A.q1[(size_t)e * NL + t] : 0.0;
+  double fq[7];
+  const bool use_box = query_free_pose(A, e, live, fq);
+  int result = 0;
+  double tc = -1.0;
+  motion_decide<T>(A, lds[team], live, qa, qb, fq, use_box, result, tc);
   if (live && t == 0) {
-    A.result[e] = have_hit ? 1 : (undecided ? 2 : 0);
-    A.t_contact[e] = have_hit ? tc : -1.0;
+    A.result[e] = result;
+    A.t_contact[e] = tc;
   }
 }
 

@@ -17,6 +17,7 @@
 #include "sim_kernels.h"
 #include "render.h"
 #include "query_team.h"
+#include "guard_team.h"
 
 using namespace rcsh;
 
@@ -78,6 +79,13 @@ struct rcsh_sim {
   float* d_slack = nullptr;          // [n][kSlackStride]: the self-contact stage's remaining gaps per pair + the joints it saw last (CheckTable::slack)
   void* d_query = nullptr;           // staging of the host-pointer collision queries (rcsh_collision_query / rcsh_motion_query), grown on demand
   size_t query_cap = 0;
+  // the environments' collision guard (guard_team.h; rcsh_env_configure_guard): its settings, and two records of [result | t_contact |
+  // blocked | hold] -- the last guarded step's (rcsh_env_guard_last) and the scratch of rcsh_env_guard_peek
+  struct GuardCfg { bool configured = false, enabled = false, block_undecided = true, truncate = true; int kinds = 0; double resolution = 0; } guard;
+  void* d_guard = nullptr;
+  bool guard_stepped = false;        // a guarded step has filled the first record
+  char* h_guard = nullptr;           // page-locked copy of that record: rcsh_env_step fetches it with its own outputs (one synchronisation)
+  bool guard_host_valid = false;     // ... and it is the last guarded step's
   int chk_unchecked = 0;             // admitted geom pairs past kMaxCheckPairs: neither checked at the end of a launch nor resolved as self contacts
   // per-environment escalation (sim_kernels.h: RunOp::esc_role): a step is the lean launch over the environments not in contact plus
   // the contact-resolving launch over the others
@@ -448,6 +456,10 @@ void build_check_table(rcsh_sim* s) {
 
 // lever[j]: how far one radian of hinge j (one metre of a slide) can move a point of any collision geom downstream of it.
 // Distances between consecutive joint anchors are constants of the links; a finger's anchor slides, so its stroke is added.
+// The additive slack of every hinge lever below (metres per radian, on top of the 1 % factor).  A chain from a hinge to a geom holds
+// at most one slide, whose stroke the lever includes: so the levers also hold for a slide up to kLeverSlack PAST its stroke.  The
+// collision guard leans on that (guard_launch: kGuardSlideTol).
+constexpr double kLeverSlack = 1e-3;
 void build_self_levers(rcsh_sim* s) {
   const DevModel& m = s->dm;
   const int na = s->narm, nl = s->nl;
@@ -479,7 +491,7 @@ void build_self_levers(rcsh_sim* s) {
     if (p >= 0) far[p] = std::max(far[p], hop[L] + stroke[L] + far[L]);
   }
   for (int j = 0; j < 12; ++j) s->self_lever[j] = 0.0;
-  for (int j = 0; j < nl; ++j) s->self_lever[j] = m.jtype[j] == kSlide ? 1.0 : 1.01 * far[j] + 1e-3;
+  for (int j = 0; j < nl; ++j) s->self_lever[j] = m.jtype[j] == kSlide ? 1.0 : 1.01 * far[j] + kLeverSlack;
   // link_lever[j][l]: the same bound for the geoms ON link l alone (j an ancestor-or-self joint of l) -- what the contact phase's slack
   // test charges a geom pair / a geom above the floor with.  The isotropic lever above takes the whole arm's reach for joint 1; the pair
   // (link 0, link 2), whose hulls stay a centimetre apart in every pose, sits 0.2 m from that axis: charged with 1.2 m per radian it was
@@ -489,7 +501,7 @@ void build_self_levers(rcsh_sim* s) {
     double acc = reach[l];  // from link l's anchor to the farthest point of a geom on l
     for (int j = l; j >= 0; j = parent(j)) {
       // acc: from joint j's anchor to the farthest point of a geom on l, over every configuration of the joints in between
-      s->link_lever[j * 12 + l] = (float)(m.jtype[j] == kSlide ? 1.0 : (1.01 * (acc + stroke[l]) + 1e-3) * 1.000001);
+      s->link_lever[j * 12 + l] = (float)(m.jtype[j] == kSlide ? 1.0 : (1.01 * (acc + stroke[l]) + kLeverSlack) * 1.000001);
       acc += hop[j] + stroke[j];
     }
   }
@@ -522,7 +534,7 @@ void build_self_levers(rcsh_sim* s) {
     }
     for (int j = l; j >= 0; j = parent(j)) {
       const double arm = j == l && m.jtype[j] != kSlide ? std::min(radial, acc) : acc + stroke[l];
-      s->link_lever[144 + j * 32 + (int)gi] = (float)(m.jtype[j] == kSlide ? 1.0 : (1.01 * arm + 1e-3) * 1.000001);
+      s->link_lever[144 + j * 32 + (int)gi] = (float)(m.jtype[j] == kSlide ? 1.0 : (1.01 * arm + kLeverSlack) * 1.000001);
       acc += hop[j] + stroke[j];
     }
   }
@@ -1000,6 +1012,8 @@ void rcsh_sim_destroy(rcsh_sim* s) {
   hipFree(s->d_cgeoms); hipFree(s->d_cverts); hipFree(s->d_pairs); hipFree(s->d_chk_geoms); hipFree(s->d_chk_ent); hipFree(s->d_lev);
   hipFree(s->d_slack);
   hipFree(s->d_query);
+  hipFree(s->d_guard);
+  if (s->h_guard) hipHostFree(s->h_guard);
   if (s->esc_stream) { hipStreamSynchronize(s->esc_stream); hipStreamDestroy(s->esc_stream); }
   if (s->esc_ev_prev) hipEventDestroy(s->esc_ev_prev);
   if (s->esc_ev_old) hipEventDestroy(s->esc_ev_old);
@@ -1903,6 +1917,8 @@ int rcsh_env_configure(rcsh_sim* s, const rcsh_env_desc* env) {
   if (env->control_mode < RCSH_MODE_JOINTS || env->control_mode > RCSH_MODE_CARTESIAN_TQUAT)
     return fail(RCSH_ERR_ARG, "bad control_mode");
   if (env->relative_to < 0 || env->relative_to > 2) return fail(RCSH_ERR_ARG, "bad relative_to");
+  if (s->guard.enabled && env->control_mode != RCSH_MODE_JOINTS)
+    return fail(RCSH_ERR_STATE, "the collision guard is enabled and guards joint-space actions only: disable it (rcsh_env_configure_guard) before configuring a Cartesian control mode");
   s->env.mode = env->control_mode;
   s->env.relative_to = env->relative_to;
   s->env.binary_gripper = env->binary_gripper;
@@ -1934,6 +1950,149 @@ int rcsh_env_reset_dev(rcsh_sim* s, const uint8_t* mask_dev, double* obs_dev, ui
   return launch_run(s, op, false);
 }
 
+// ---- the collision guard (csrc/guard_team.h)
+namespace {
+struct GuardRecord { int32_t* result; double* t_contact; uint8_t* blocked; uint8_t* hold; };
+size_t guard_record_bytes(const rcsh_sim* s) { return align8(8 * (size_t)s->n) + align8(4 * (size_t)s->n) + 2 * align8((size_t)s->n); }
+GuardRecord guard_record(const rcsh_sim* s, int which) {  // 0: the last guarded step, 1: the peek's scratch
+  char* d = static_cast<char*>(s->d_guard) + (size_t)which * guard_record_bytes(s);
+  const size_t n = (size_t)s->n;
+  GuardRecord r{};
+  r.t_contact = reinterpret_cast<double*>(d);
+  r.result = reinterpret_cast<int32_t*>(d + align8(8 * n));
+  r.blocked = reinterpret_cast<uint8_t*>(d + align8(8 * n) + align8(4 * n));
+  r.hold = r.blocked + align8(n);
+  return r;
+}
+__global__ void k_guard_fill(int32_t* result, double* t_contact, uint8_t* blocked, uint8_t* hold, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) { result[i] = 0; t_contact[i] = -1.0; blocked[i] = 0; if (hold) hold[i] = kGuardLive; }
+}
+// RobotSimWrapper.step's `truncated` of a blocked environment (info row, byte 4), after the stepping launch
+__global__ void k_guard_truncate(uint8_t* info, const uint8_t* blocked, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && blocked[i]) info[(size_t)i * 8 + 4] = 1;
+}
+// the guard kernel over every environment for the actions at action_dev, into device buffers
+int guard_launch(rcsh_sim* s, const double* action_dev, int32_t* result, double* t_contact, uint8_t* blocked, uint8_t* hold) {
+  if (s->cgeoms.empty()) {  // (a robot without collision geometry: nothing can be in contact, as the queries answer)
+    hipLaunchKernelGGL(k_guard_fill, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, result, t_contact, blocked, hold, s->n);
+    HIP_TRY(hipGetLastError());
+    return RCSH_OK;
+  }
+  GuardArgs G{};
+  const bool box = (s->guard.kinds & kQueryBox) && s->box.present;
+  G.Q = query_args(s, s->n, s->guard.kinds & (box ? kQueryKinds : (kQueryFloor | kQuerySelf)));
+  G.Q.resolution = s->guard.resolution;
+  // A finger of the open hand rests ON its joint limit, and the soft limit lets it through by some 10 um (measured: up to 44 um in a
+  // rollout): for the motion query such a row has left the stroke the levers were built for and is never certified -- the guard
+  // would block a quarter of a batch for it.  The levers hold further than the query admits: build_self_levers charges a hinge
+  // 1.01 (d + stroke) + kLeverSlack for a geom whose distance bound is d + stroke, and a chain holds one slide, so a slide up to
+  // kLeverSlack past its stroke is covered by that additive term alone.  The guard admits half of it.
+  constexpr double kGuardSlideTol = 5e-4;
+  static_assert(kGuardSlideTol <= 0.5 * kLeverSlack, "the guard's slide tolerance lives inside the levers' additive slack");
+  for (int L = 0; L < 12; ++L) { G.Q.slide_lo[L] -= kGuardSlideTol; G.Q.slide_hi[L] += kGuardSlideTol; }
+  G.S = s->S;
+  G.flags = s->flags;
+  G.action = action_dev;
+  G.env = s->env;
+  G.box_field = box ? field_of(s, "box") + kBoxQ : -1;
+  G.block_undecided = s->guard.block_undecided ? 1 : 0;
+  G.result = result; G.t_contact = t_contact; G.blocked = blocked; G.hold = hold;
+  hipError_t err = hipSuccess;
+  const bool ok = dispatch_topology(s->narm, s->grip, [&](auto topo) {
+    using T = decltype(topo);
+    hipLaunchKernelGGL(k_env_guard<T>, dim3((s->n + 3) / 4), dim3(64), 0, s->stream, G);
+    err = hipGetLastError();
+  });
+  if (!ok) return fail(RCSH_ERR_MODEL, "no kernel instantiated for this archetype");
+  if (err != hipSuccess) return fail(RCSH_ERR_DEVICE, std::string("collision guard launch: ") + hipGetErrorString(err));
+  return RCSH_OK;
+}
+}  // namespace
+
+int rcsh_env_configure_guard(rcsh_sim* s, const rcsh_guard_desc* g) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (!s->env_configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure first");
+  if (!g) return fail(RCSH_ERR_ARG, "null guard description");
+  if (g->kinds < 1 || g->kinds > kQueryKinds) return fail(RCSH_ERR_ARG, "the guard's kinds mask must select at least one of bit 0 floor, 1 self, 2 free body, and nothing else");
+  if (!(g->resolution > 0.0) || !std::isfinite(g->resolution)) return fail(RCSH_ERR_ARG, "resolution must be positive and finite");
+  if (s->env.mode != RCSH_MODE_JOINTS)
+    return fail(RCSH_ERR_STATE, "the collision guard guards joint-space actions only: the environments are configured for a Cartesian control mode");
+  int rc = query_check(s, s->n, g->kinds, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  if (!s->d_guard) HIP_TRY(hipMalloc(&s->d_guard, 2 * guard_record_bytes(s)));
+  if (!s->h_guard) { void* p = nullptr; HIP_TRY(hipHostMalloc(&p, guard_record_bytes(s), hipHostMallocDefault)); s->h_guard = (char*)p; }
+  s->guard.configured = true;
+  s->guard.enabled = g->enabled != 0;
+  s->guard.kinds = g->kinds;
+  s->guard.resolution = g->resolution;
+  s->guard.block_undecided = g->block_undecided != 0;
+  s->guard.truncate = g->truncate != 0;
+  return RCSH_OK;
+}
+
+int rcsh_env_guard_peek_dev(rcsh_sim* s, const double* action_dev, int32_t* result_dev, double* t_contact_dev, uint8_t* blocked_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (!s->guard.configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure_guard first");
+  if (s->env.mode != RCSH_MODE_JOINTS) return fail(RCSH_ERR_STATE, "the collision guard answers for joint-space actions only: the environments are configured for a Cartesian control mode");
+  if (!action_dev || !result_dev || !t_contact_dev || !blocked_dev) return fail(RCSH_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(s->device));
+  return guard_launch(s, action_dev, result_dev, t_contact_dev, blocked_dev, nullptr);
+}
+
+int rcsh_env_guard_peek(rcsh_sim* s, const double* action, int32_t* result, double* t_contact, uint8_t* blocked) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (!s->guard.configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure_guard first");
+  if (s->env.mode != RCSH_MODE_JOINTS) return fail(RCSH_ERR_STATE, "the collision guard answers for joint-space actions only: the environments are configured for a Cartesian control mode");
+  if (!action) return fail(RCSH_ERR_ARG, "null action");
+  const size_t n = (size_t)s->n, na = n * (size_t)s->narm;
+  int rc = query_finite(action, na, "action");
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = query_stage(s, 8 * na))) return rc;
+  double* d_action = static_cast<double*>(s->d_query);
+  const GuardRecord r = guard_record(s, 1);
+  HIP_TRY(hipMemcpyAsync(d_action, action, 8 * na, hipMemcpyHostToDevice, s->stream));
+  if ((rc = guard_launch(s, d_action, r.result, r.t_contact, r.blocked, nullptr))) return rc;
+  if (result) HIP_TRY(hipMemcpyAsync(result, r.result, 4 * n, hipMemcpyDeviceToHost, s->stream));
+  if (t_contact) HIP_TRY(hipMemcpyAsync(t_contact, r.t_contact, 8 * n, hipMemcpyDeviceToHost, s->stream));
+  if (blocked) HIP_TRY(hipMemcpyAsync(blocked, r.blocked, n, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RCSH_OK;
+}
+
+int rcsh_env_guard_last_dev(rcsh_sim* s, const int32_t** result_dev, const double** t_contact_dev, const uint8_t** blocked_dev) {
+  REQUIRE_SIM(s);
+  if (!s->guard.configured || !s->guard_stepped) return fail(RCSH_ERR_STATE, "no guarded step has run");
+  const GuardRecord r = guard_record(s, 0);
+  if (result_dev) *result_dev = r.result;
+  if (t_contact_dev) *t_contact_dev = r.t_contact;
+  if (blocked_dev) *blocked_dev = r.blocked;
+  return RCSH_OK;
+}
+
+int rcsh_env_guard_last(rcsh_sim* s, int32_t* result, double* t_contact, uint8_t* blocked) {
+  REQUIRE_SIM(s);
+  if (!s->guard.configured || !s->guard_stepped) return fail(RCSH_ERR_STATE, "no guarded step has run");
+  const size_t n = (size_t)s->n;
+  if (s->guard_host_valid) {  // (rcsh_env_step brought the record along with its outputs)
+    const char* hg = s->h_guard;
+    if (t_contact) std::memcpy(t_contact, hg, 8 * n);
+    if (result) std::memcpy(result, hg + align8(8 * n), 4 * n);
+    if (blocked) std::memcpy(blocked, hg + align8(8 * n) + align8(4 * n), n);
+    return RCSH_OK;
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  const GuardRecord r = guard_record(s, 0);
+  if (result) HIP_TRY(hipMemcpyAsync(result, r.result, 4 * n, hipMemcpyDeviceToHost, s->stream));
+  if (t_contact) HIP_TRY(hipMemcpyAsync(t_contact, r.t_contact, 8 * n, hipMemcpyDeviceToHost, s->stream));
+  if (blocked) HIP_TRY(hipMemcpyAsync(blocked, r.blocked, n, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RCSH_OK;
+}
+
 int rcsh_env_step_dev(rcsh_sim* s, const double* action_dev, const float* gripper_dev, double* obs_dev, uint8_t* info_dev,
                       double* gw_dev, int32_t* substeps_dev) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
@@ -1942,6 +2101,15 @@ int rcsh_env_step_dev(rcsh_sim* s, const double* action_dev, const float* grippe
   HIP_TRY(hipSetDevice(s->device));
   RunOp op{};
   op.apply_action = 1;
+  const bool guarded = s->guard.enabled && s->env.mode == RCSH_MODE_JOINTS;  // (rcsh_env_configure refuses a Cartesian mode under a guard)
+  if (guarded) {
+    // the guard decides on the stream ahead of the stepping launch, which reads the verdicts as its mask (RunOp::apply_action == 2)
+    const GuardRecord r = guard_record(s, 0);
+    int rc = guard_launch(s, action_dev, r.result, r.t_contact, r.blocked, r.hold);
+    if (rc) return rc;
+    op.apply_action = 2;
+    op.mask = r.hold;
+  }
   if (s->env.mode != RCSH_MODE_JOINTS) {
     // Cartesian modes: wrappers' action() + IK run in their own launch, the stepping launch follows on the stream
     CartOp cop{};
@@ -1959,7 +2127,14 @@ int rcsh_env_step_dev(rcsh_sim* s, const double* action_dev, const float* grippe
   op.action = action_dev; op.gripper = gripper_dev;
   op.obs = obs_dev; op.info = info_dev; op.gripper_width = gw_dev; op.substeps = substeps_dev;
   op.task = s->pending_task;
-  return launch_run(s, op, true);
+  int rc = launch_run(s, op, true);
+  if (rc) return rc;
+  if (guarded) { s->guard_stepped = true; s->guard_host_valid = false; }
+  if (guarded && s->guard.truncate && info_dev) {
+    hipLaunchKernelGGL(k_guard_truncate, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, info_dev, guard_record(s, 0).blocked, s->n);
+    HIP_TRY(hipGetLastError());
+  }
+  return RCSH_OK;
 }
 
 // ---- task layer of the pick-up scene: SimTaskEnvCreator = SimEnvCreator + RandomCubePos under the RobotSimWrapper +
@@ -2105,7 +2280,11 @@ int rcsh_env_step(rcsh_sim* s, const double* action, const float* gripper, doubl
   if (info) HIP_TRY(hipMemcpyAsync(s->h_pin + L.info, s->d_bytes, (size_t)s->n * 8, hipMemcpyDeviceToHost, s->stream));
   if (gw) HIP_TRY(hipMemcpyAsync(s->h_pin + L.gw, s->d_stage, sizeof(double) * s->n, hipMemcpyDeviceToHost, s->stream));
   if (substeps) HIP_TRY(hipMemcpyAsync(s->h_pin + L.sub, s->d_ints, sizeof(int32_t) * s->n, hipMemcpyDeviceToHost, s->stream));
+  const bool guard_record_too = s->guard.enabled && s->guard_stepped && s->h_guard;
+  // (the guard's record -- t_contact, result, blocked: one contiguous piece -- rides along: rcsh_env_guard_last then needs no second wait)
+  if (guard_record_too) HIP_TRY(hipMemcpyAsync(s->h_guard, s->d_guard, align8(8 * (size_t)s->n) + align8(4 * (size_t)s->n) + (size_t)s->n, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
+  s->guard_host_valid = guard_record_too;
   if (obs) std::memcpy(obs, s->h_pin + L.obs, sizeof(double) * s->n * ow);
   if (info) std::memcpy(info, s->h_pin + L.info, (size_t)s->n * 8);
   if (gw) std::memcpy(gw, s->h_pin + L.gw, sizeof(double) * s->n);

@@ -97,13 +97,14 @@ struct TaskCfg {
 
 struct RunOp {
   int32_t do_reset;       // env.reset(): gripper reset, sim reset, robot reset (then nsteps = 1)
-  int32_t apply_action;   // env.step(): wrappers' action() + RobotEnv.step
+  int32_t apply_action;   // env.step(): wrappers' action() + RobotEnv.step; 2: with the collision guard's verdicts in `mask` (bit 1 of an
+                          // environment's byte: RobotEnv.step gets its current joint position instead of the action's command)
   int32_t nsteps;         // >= 0: Sim.step(nsteps); < 0: Sim.step_until_convergence()
   int32_t write_obs;
   int32_t observe_only;   // an observation-only pass (nsteps = 0) that must leave the rendering records of the last stepping launch alone
   int32_t check;          // end the launch with the check for contacts nobody resolves (check_team.h; the host decides the cadence);
                           // 2: certifying -- whatever cannot be PROVEN apart by more than it travelled during the launch counts as a hit
-  const uint8_t* mask;    // optional, device
+  const uint8_t* mask;    // optional, device: a zero byte sits the environment out
   const double* action;   // [n][action_width], device
   const float* gripper;   // [n], device
   double* obs;            // [n][obs_width]
@@ -582,6 +583,11 @@ __device__ __forceinline__ void env_prologue(const Params& P, const RunOp& op, c
       }
       r.flags |= kHasLastAction;
     }
+    // ---- CollisionGuard (guard_team.h): a blocked environment is commanded to stay where it is
+    if (op.apply_action == 2 && (op.mask[e] & 2)) {
+#pragma unroll
+      for (int i = 0; i < T::NARM; ++i) a[i] = r.st.q(i);
+    }
     // ---- GripperWrapper.action (base.py:721-735)
     if (T::GRIP && P.grip.present && op.gripper) {
       float g = in.gripper();
@@ -653,6 +659,11 @@ __device__ __forceinline__ void env_prologue_team(const Params& P, const RunOp& 
       }
       flags |= kHasLastAction;
     }
+    // ---- CollisionGuard (reference python/rcs/envs/sim.py:196-204; guard_team.h decides, ahead of this launch): the wrapper sits
+    // between the relative action space and RobotEnv.step -- a blocked environment's command becomes its current joint position,
+    // unclamped; what the relative action space remembers has advanced on the original action, above.  (Wave-uniform test; a launch
+    // without a guard never reads the byte.)
+    if (op.apply_action == 2 && joint && (op.mask[e] & 2)) a = r.st.q(ti);
     // ---- GripperWrapper.action (base.py:721-735)
     if (T::GRIP && P.grip.present && op.gripper) {
       float g = in_grip;

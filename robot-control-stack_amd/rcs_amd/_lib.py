@@ -156,6 +156,10 @@ class EnvDesc(C.Structure):
     ]
 
 
+class GuardDesc(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("kinds", C.c_int32), ("resolution", C.c_double), ("block_undecided", C.c_int32), ("truncate", C.c_int32)]
+
+
 # every symbol include/rcs_hip.h declares; load() fails if one is missing
 EXPORTS = (
     "rcsh_last_error", "rcsh_abi_version", "rcsh_device_count", "rcsh_sim_create", "rcsh_sim_destroy",
@@ -185,6 +189,7 @@ EXPORTS = (
     "rcsh_sim_contact_escalated",
     "rcsh_sim_contact_overflow",
     "rcsh_collision_query", "rcsh_collision_query_dev", "rcsh_motion_query", "rcsh_motion_query_dev",
+    "rcsh_env_configure_guard", "rcsh_env_guard_peek", "rcsh_env_guard_peek_dev", "rcsh_env_guard_last", "rcsh_env_guard_last_dev",
 )
 
 _lib = None
@@ -266,6 +271,11 @@ def load() -> C.CDLL:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     for fn in (L.rcsh_motion_query, L.rcsh_motion_query_dev):
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
+    L.rcsh_env_configure_guard.argtypes = [C.c_void_p, C.POINTER(GuardDesc)]
+    for fn in (L.rcsh_env_guard_peek, L.rcsh_env_guard_peek_dev):
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rcsh_env_guard_last.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rcsh_env_guard_last_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     _lib = L
     return L
 

@@ -33,6 +33,11 @@ class VecSimEnv:
     obs dict: ``tquat [N,7]``, ``joints [N,dof]``, ``xyzrpy [N,6]`` (+ ``gripper [N]``);
     info dict: ``collision``, ``ik_success``, ``is_sim_converged`` (+ ``gripper_width``, ``is_grasped``), all ``[N]``;
     ``step`` returns ``(obs, reward [N] = 0, terminated [N] = False, truncated [N], info)``.
+
+    With a collision guard (``SimEnvCreator()(..., collision_guard=True)`` or :meth:`configure_guard`) every step first decides, on
+    the device, whether the straight joint-space motion from where each arm is to where its action sends it is proven free of
+    contact (csrc/guard_team.h).  A blocked environment is commanded to stay where it is and -- with ``truncate_on_collision`` -- is
+    reported ``terminated`` and ``truncated``; ``info`` gains ``guard_blocked``, ``guard_result`` and ``guard_t_contact``.
     """
 
     def __init__(self, simulation: sim.Sim, robot: sim.SimRobot, gripper: sim.SimGripper | None,
@@ -82,6 +87,78 @@ class VecSimEnv:
         #   "flag":    report only -- with a Sim created with resolve_robot_contacts=False the environment steps on unresolved (the arm
         #              passes through the floor / itself) and the caller decides (mask it, reset it, discard the episode).
         self.on_unresolved_contact = "resolve"
+        self.guard_enabled = False
+        self.guard_truncates = True
+
+    # ---- collision guard (reference python/rcs/envs/sim.py:156-287: CollisionGuard between RelativeActionSpace and RobotEnv.step)
+    def default_guard_kinds(self) -> int:
+        """Everything the scene has where there is no free body; floor | self where there is one: a pick-up task must be allowed
+        to touch its cube, so guarding against the free body is opt-in (``kinds=7``)."""
+        R = sim.SimRobot
+        has_free = bool(getattr(self.sim.model, "free_bodies", []))
+        return R.COLLISION_FLOOR | R.COLLISION_SELF if has_free else R.COLLISION_ALL
+
+    def configure_guard(self, enabled: bool = True, kinds: int | None = None, resolution: float = 1e-3, block_undecided: bool = True,
+                        truncate_on_collision: bool = True) -> None:
+        """Configure the batched collision guard (joint-space control modes only; RuntimeError otherwise).
+
+        An action passes only when the straight joint-space motion from the arm's current configuration to the absolute joint
+        command the action resolves to is PROVEN free of the selected ``kinds`` of contact (the motion query's lever certificate,
+        :meth:`rcs_amd.sim.SimRobot.check_motion`; finger slides and the free body as they are now).  ``guard_result`` 1 (a contact
+        was found) blocks; 2 (neither proven nor refuted down to ``resolution``) blocks when ``block_undecided``.  A blocked
+        environment's arm is commanded to its current joint position; the relative action space advances on the original action and
+        the gripper command applies unchanged.  Two deviations from the reference, on purpose: the decision is kinematic and
+        certifying, not a shadow simulation (which the reference marks as not working); and every environment of the batch steps -- a
+        blocked one with the hold command, its fresh observation returned -- where the reference returns the previous observation.
+        ``truncate_on_collision`` only decides whether blocked environments are reported ``terminated`` and ``truncated``.
+        ``enabled=False`` leaves the steps unguarded (:meth:`check_action` still answers)."""
+        d = _lib.GuardDesc()
+        d.enabled = int(bool(enabled))
+        d.kinds = self.default_guard_kinds() if kinds is None else int(kinds)
+        d.resolution = float(resolution)
+        d.block_undecided = int(bool(block_undecided))
+        d.truncate = int(bool(truncate_on_collision))
+        _lib.check(self._L.rcsh_env_configure_guard(self.sim._h, C.byref(d)))
+        self.guard_enabled = bool(enabled)
+        self.guard_truncates = bool(truncate_on_collision)
+
+    def check_action(self, action):
+        """The guard's decision for an action batch (``{"joints": [N, dof]}`` or the array), without stepping and without writing any
+        state: ``(blocked bool [N], result int32 [N], t_contact [N])``.  Needs :meth:`configure_guard` (``enabled`` or not)."""
+        n = self.n_envs
+        a = action[self.action_key] if isinstance(action, dict) else action
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (n, self.action_width)))
+        result = np.zeros(n, dtype=np.int32)
+        tc = np.zeros(n)
+        blocked = np.zeros(n, dtype=np.uint8)
+        _lib.check(self._L.rcsh_env_guard_peek(self.sim._h, _lib.ptr(a), _lib.ptr(result), _lib.ptr(tc), _lib.ptr(blocked)))
+        return blocked.astype(bool), result, tc
+
+    def guard_last(self):
+        """``(blocked, result, t_contact)`` of the most recent guarded step (what ``step`` puts into ``info``; for ``step_dev`` loops)."""
+        n = self.n_envs
+        result = np.zeros(n, dtype=np.int32)
+        tc = np.zeros(n)
+        blocked = np.zeros(n, dtype=np.uint8)
+        _lib.check(self._L.rcsh_env_guard_last(self.sim._h, _lib.ptr(result), _lib.ptr(tc), _lib.ptr(blocked)))
+        return blocked.astype(bool), result, tc
+
+    def guard_last_dev(self) -> tuple[int, int, int]:
+        """Device pointers ``(blocked uint8 [N], result int32 [N], t_contact float64 [N])`` of the guarded steps' record: valid for the
+        Sim's life, rewritten by every guarded step."""
+        r, t, b = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(self._L.rcsh_env_guard_last_dev(self.sim._h, C.byref(r), C.byref(t), C.byref(b)))
+        return int(b.value), int(r.value), int(t.value)
+
+    def _guard_info(self, i: dict[str, Any]):
+        """info["guard_*"] of a guarded step; returns ``blocked`` where it truncates (else None)."""
+        if not self.guard_enabled:
+            return None
+        blocked, result, tc = self.guard_last()
+        i["guard_blocked"] = blocked
+        i["guard_result"] = result
+        i["guard_t_contact"] = tc
+        return blocked if self.guard_truncates else None
 
     def _after_step(self, info) -> None:
         if self.on_unresolved_contact == "resolve" and not self.sim.resolve_robot_contacts and info[:, 7].any():
@@ -155,14 +232,20 @@ class VecSimEnv:
         # last reset (csrc/check_team.h): MuJoCo would have resolved it, so from that step on the trajectory is not MuJoCo's
         i["contact_unresolved"] = info[:, 7].astype(bool)
         self._after_step(info)
-        truncated = info[:, 4].astype(bool)
-        return o, np.zeros(n), np.zeros(n, dtype=bool), truncated, i
+        truncated = info[:, 4].astype(bool)  # (a truncating guard has set it for the environments it blocked)
+        terminated = np.zeros(n, dtype=bool)
+        stop = self._guard_info(i)
+        if stop is not None:
+            terminated |= stop
+            truncated |= stop
+        return o, np.zeros(n), terminated, truncated, i
 
     # ---- device-pointer interface for resident rollouts (pointers are integers / c_void_p)
     def reset_dev(self, obs_ptr, info_ptr=None, gw_ptr=None, mask_ptr=None) -> None:
         _lib.check(self._L.rcsh_env_reset_dev(self.sim._h, C.c_void_p(mask_ptr), C.c_void_p(obs_ptr), C.c_void_p(info_ptr), C.c_void_p(gw_ptr)))
 
     def step_dev(self, action_ptr, gripper_ptr, obs_ptr, info_ptr=None, gw_ptr=None, substeps_ptr=None) -> None:
+        """One resident step.  A configured guard applies here too: its record is at :meth:`guard_last_dev` / :meth:`guard_last`."""
         _lib.check(self._L.rcsh_env_step_dev(self.sim._h, C.c_void_p(action_ptr), C.c_void_p(gripper_ptr), C.c_void_p(obs_ptr),
                                              C.c_void_p(info_ptr), C.c_void_p(gw_ptr), C.c_void_p(substeps_ptr)))
 
@@ -261,7 +344,12 @@ class VecPickCubeEnv(VecSimEnv):
         i["box_qpos"] = task[:, :7].copy()
         success = task[:, 8] != 0
         i["success"] = success
-        return o, task[:, 7].copy(), success, info[:, 4].astype(bool), i
+        terminated, truncated = success.copy(), info[:, 4].astype(bool)
+        stop = self._guard_info(i)  # (the task keeps its own reward for a blocked environment)
+        if stop is not None:
+            terminated |= stop
+            truncated |= stop
+        return o, task[:, 7].copy(), terminated, truncated, i
 
     def step_task_dev(self, action_ptr, gripper_ptr, obs_ptr, info_ptr=None, gw_ptr=None, substeps_ptr=None, task_ptr=None) -> None:
         _lib.check(self._L.rcsh_env_step_task_dev(self.sim._h, C.c_void_p(action_ptr), C.c_void_p(gripper_ptr), C.c_void_p(obs_ptr),
@@ -287,13 +375,20 @@ def random_object_qpos(init_object_pose: common.Pose, n_envs: int, include_posit
 
 
 class SimEnvCreator:
+    """Reference python/rcs/envs/creators.py:43-128 for N environments.  ``collision_guard=True`` returns the env with the batched
+    collision guard configured at its defaults (:meth:`VecSimEnv.configure_guard`: a kinematic, certifying guard decided on the
+    device, in place of the reference's shadow simulation); it needs a joint-space control mode."""
+
     def __call__(self, control_mode: ControlMode, robot_cfg: sim.SimRobotConfig, collision_guard: bool = False,
                  gripper_cfg: sim.SimGripperConfig | None = None, sim_cfg: sim.SimConfig | None = None,
                  hand_cfg=None, cameras=None, max_relative_movement: float | tuple[float, float] | None = None,
                  relative_to: RelativeTo = RelativeTo.LAST_STEP, sim_wrapper=None, n_envs: int = 1, device: int = 0,
                  resolve_robot_contacts=None) -> VecSimEnv:
-        if hand_cfg is not None or sim_wrapper is not None or collision_guard:
-            raise NotImplementedError("hands, sim_wrapper and collision_guard are outside this backend's hot path")
+        if hand_cfg is not None or sim_wrapper is not None:
+            raise NotImplementedError("hands and sim_wrapper are outside this backend's hot path")
+        if collision_guard and control_mode != ControlMode.JOINTS:
+            raise NotImplementedError("collision_guard guards joint-space actions only (ControlMode.JOINTS): the Cartesian modes' IK runs in a "
+                                      "launch of its own, and a guard between it and the stepping launch is not built yet")
         simulation = sim.Sim(robot_cfg.mjcf_scene_path, sim_cfg, n_envs=n_envs, device=device, resolve_robot_contacts=resolve_robot_contacts)
         robot = sim.SimRobot(simulation, None, robot_cfg)
         gripper = sim.SimGripper(simulation, gripper_cfg) if gripper_cfg is not None else None
@@ -302,7 +397,10 @@ class SimEnvCreator:
             from ..camera import SimCameraSet
 
             camera_set = SimCameraSet(simulation, cameras, physical_units=True, render_on_demand=True)
-        return VecSimEnv(simulation, robot, gripper, control_mode, max_relative_movement, relative_to, camera_set=camera_set)
+        venv = VecSimEnv(simulation, robot, gripper, control_mode, max_relative_movement, relative_to, camera_set=camera_set)
+        if collision_guard:
+            venv.configure_guard()
+        return venv
 
 
 class SimTaskEnvCreator:

@@ -41,9 +41,11 @@ def robot_cfg_for(robot: str) -> sim.SimRobotConfig:
 
 def make_vec_env(n_envs: int, async_control: bool, gripper: bool = True, relative: bool = True, control_mode=None, device: int = 0,
                  max_relative_movement=None, robot: str = "fr3", relative_to: str = "last_step", frequency: int = 30,
-                 max_convergence_steps: int = 500, robot_cfg: sim.SimRobotConfig | None = None, resolve_robot_contacts=None):
+                 max_convergence_steps: int = 500, robot_cfg: sim.SimRobotConfig | None = None, resolve_robot_contacts=None,
+                 collision_guard: bool = False):
     """`n_envs` environments of one robot type on GPU `device`.  `robot_cfg` overrides the robot's default configuration
-    (its scene decides the kernel archetype); only the FR3, SO101 and xarm7_pick scenes carry a gripper."""
+    (its scene decides the kernel archetype); only the FR3, SO101 and xarm7_pick scenes carry a gripper.  `collision_guard`: the
+    batched collision guard at its defaults (VecSimEnv.configure_guard; joint-space control only)."""
     cfg = sim.SimConfig(async_control=async_control, realtime=False, frequency=frequency, max_convergence_steps=max_convergence_steps)
     mode = control_mode or ControlMode.JOINTS
     if relative and max_relative_movement is None:
@@ -53,7 +55,7 @@ def make_vec_env(n_envs: int, async_control: bool, gripper: bool = True, relativ
     gripper_cfg = ((so101_sim_gripper_cfg() if robot == "so101" else xarm7_pick_sim_gripper_cfg() if robot == "xarm7_pick" else default_sim_gripper_cfg())
                    if gripper else None)
     return SimEnvCreator()(
-        mode, robot_cfg if robot_cfg is not None else robot_cfg_for(robot),
+        mode, robot_cfg if robot_cfg is not None else robot_cfg_for(robot), collision_guard=collision_guard,
         gripper_cfg=gripper_cfg,
         sim_cfg=cfg, max_relative_movement=max_relative_movement if relative else None,
         relative_to=RelativeTo.LAST_STEP if relative_to == "last_step" else RelativeTo.CONFIGURED_ORIGIN,
