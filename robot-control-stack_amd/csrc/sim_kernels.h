@@ -129,13 +129,14 @@ struct RunOp {
                           // certificate's margins are the joints' travel over ONE launch: a 500-substep launch that moves a joint five degrees
                           // cannot clear pairs that are 15 mm apart in every pose, a quarter of it can -- and an environment that fails is
                           // redone for that piece only
-  // Role 2 in two parts (esc_part): the environments that WERE escalated when the step began do not depend on the step's lean launch --
-  // part 1 steps them on a stream of its own, next to the lean launch, and leaves the masks alone; part 2, behind both, redoes the newly
-  // flagged ones and merges.  0: one launch does both (behind the lean one).  The host splits when it knows of escalated environments.
+  // esc_part / esc_seq / esc_host: what is left of a dropped form of role 2 ("What the round's measurements say", item 7).
+  // The host leaves all three zero: esc_select takes its esc_part == 0 arms and the two blocks that test esc_host never run.  Folding
+  // esc_select or deleting those blocks moves the register allocation of some instantiations (SGPR spills; VGPR spills and 16-32 bytes
+  // of scratch: profiles/retire_split_regs.txt), so they stay until those kernels are next retuned.
   int32_t esc_part;
-  int32_t esc_seq;        // role 1: the step's number, for esc_host
+  int32_t esc_seq;
   int32_t conv_resume;    // this launch CONTINUES a step_until_convergence begun by an earlier one: substep count, verdicts and the cap carry over
-  uint32_t* esc_host;     // [2] host memory: the last step whose lean launch has (all but) ended, the escalated count it started with
+  uint32_t* esc_host;
   uint64_t* esc;          // [3][(n + 63) / 64]
   uint32_t* esc_ctr;      // [0] workgroups of the role-2 launch that are done, [1] environments escalated after the last merge,
                           // [2] environments the role-1 launch of this step has flagged (a role-2 launch that finds [1] = [2] = 0 ends at once)
@@ -844,7 +845,7 @@ __device__ __attribute__((always_inline)) inline void run_team_body(const Params
   // rollout that touches nothing -- ends here, before a single load has gone out: two scalar loads; a wavefront that has asked for
   // its tables waits for them before it may end, 4.5 us for the launch instead of 1.5)
   if constexpr (CON) {
-    if (opk.esc_role == 2 && opk.esc_ctr[1] == 0 && (opk.esc_part == 1 || opk.esc_ctr[2] == 0)) return;
+    if (opk.esc_role == 2 && opk.esc_ctr[1] == 0 && opk.esc_ctr[2] == 0) return;
   }
   LdsCopy<sizeof(Params) / 8> cp_params;
   LdsCopy<sizeof(RunOp) / 8> cp_op;
@@ -882,7 +883,7 @@ __device__ __attribute__((always_inline)) inline void run_team_body(const Params
       // (role 2 may spread its environments one per workgroup: every workgroup asks)
       const int pick = esc_select(opk, Pk.n, e_slot0, team, esc_redo, true);
       if (__ballot(pick >= 0) == 0) {  // no environment for any of this workgroup's four slots
-        if (opk.esc_part != 1) esc_finish(opk, Pk.n);
+        esc_finish(opk, Pk.n);
         return;
       }
       e = pick >= 0 ? pick : Pk.n;
@@ -962,7 +963,7 @@ __device__ __attribute__((always_inline)) inline void run_team_body(const Params
   const bool live = in_range && !((esc_word >> (e & 63)) & 1ull);
   const bool leader = t == 0 && live;
   if (esc_role == 1 && __ballot(live) == 0) {  // (every environment of this workgroup is on the contact-resolving kernel, or out of range)
-    if (blockIdx.x == 0 && threadIdx.x == 0 && opk.esc_host) {  // (the host's hint: see the launch's end)
+    if (blockIdx.x == 0 && threadIdx.x == 0 && opk.esc_host) {  // (never taken: RunOp::esc_host)
       __hip_atomic_store(opk.esc_host + 1, opk.esc_ctr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __hip_atomic_store(opk.esc_host, (uint32_t)opk.esc_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
@@ -1575,11 +1576,9 @@ __device__ __attribute__((always_inline)) inline void run_team_body(const Params
   }
   if (esc_role == 2) {
     if (esc_leave) atomicOr(reinterpret_cast<unsigned long long*>(lop.esc + 2 * ((P.n + 63) >> 6) + (e >> 6)), 1ull << (e & 63));
-    if (lop.esc_part != 1) esc_finish(lop, P.n);
+    esc_finish(lop, P.n);
   }
-  if (esc_role == 1 && blockIdx.x == 0 && threadIdx.x == 0 && lop.esc_host) {
-    // for the host, which runs ahead of the device: which step's lean launch has (all but) ended, and how many environments were
-    // escalated when it began (host memory; read without synchronisation: a hint for how the next steps are enqueued, nothing more)
+  if (esc_role == 1 && blockIdx.x == 0 && threadIdx.x == 0 && lop.esc_host) {  // (never taken: RunOp::esc_host)
     __hip_atomic_store(lop.esc_host + 1, lop.esc_ctr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(lop.esc_host, (uint32_t)lop.esc_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
