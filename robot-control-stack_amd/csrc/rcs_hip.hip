@@ -43,6 +43,31 @@ constexpr int kProfRing = 4096;
 }  // namespace
 
 struct CopyCarrier;
+// a buffer that grows on demand (grow_device / grow_pinned)
+struct Grown { void* p = nullptr; size_t cap = 0; };
+// Device staging of the host-pointer entry points: one allocation, cut by stage_layout -- and nowhere else -- into typed slices that
+// do not overlap; each starts on a 256-byte boundary.  A slice with two names carries two contents that no single entry point uses together.
+struct Staging {
+  void* base = nullptr;
+  int action_w = 0, obs_w = 0, q0_w = 0;  // doubles per environment of `action`, `obs` and `q0`
+  uint8_t* mask = nullptr;       // [n]: the caller's mask
+  uint8_t* inv_mask = nullptr;   // [n]: its complement (observe_unmasked)
+  uint8_t* info = nullptr;       // [n][kInfoBytes]: the env layer's info rows
+  uint8_t* flag = nullptr;       // [n]: one flag bit as bytes (flag_host) | the IK's success (run_ik)
+  int32_t* substeps = nullptr;   // [n]: the env-step's substeps | the IK's iterations (run_ik)
+  float* grip_cmd = nullptr;     // [n]: the env-step's gripper command
+  double* grip_width = nullptr;  // [n]: gripper widths out
+  double* action = nullptr;      // [n][action_w]: the env-step's action
+  double* box_task = nullptr;    // [n][kTaskWidth]: the box pose in (7 wide, rcsh_env_reset_task) | the task rows out (rcsh_env_step_task)
+  double* obs = nullptr;         // [n][obs_w]: observations | the IK's output (nl or 7 wide, run_ik)
+  double* wide = nullptr;        // [n][kStageWidth]: a field group on its way into or out of the state (scatter_host / gather_host)
+  double* pose = nullptr;        // [n][7]: target poses (run_ik, rcsh_robot_set_cartesian_position)
+  double* q0 = nullptr;          // [n][q0_w]: the IK's start configurations
+  double* tcp = nullptr;         // [7]: the IK's tcp offset
+};
+// Page-locked staging of the env layer's host forms, between the caller's arrays and the device slices (offsets in bytes):
+// [action | gripper | box pose | obs | info | gripper width | substeps | task]
+struct PinLayout { size_t action, gripper, box, obs, info, gw, sub, task, total; };
 struct rcsh_sim {
   int device = 0;
   int kernel = RCSH_KERNEL_AUTO;
@@ -77,8 +102,7 @@ struct rcsh_sim {
   float link_lever[12 * 12 + 12 * 32] = {0};  // contact_types.h: CheckTable::lev ([joint][link]), then the same per GEOM ([joint][geom], kLevGeom)
   float* d_lev = nullptr;
   float* d_slack = nullptr;          // [n][kSlackStride]: the self-contact stage's remaining gaps per pair + the joints it saw last (CheckTable::slack)
-  void* d_query = nullptr;           // staging of the host-pointer collision queries (rcsh_collision_query / rcsh_motion_query), grown on demand
-  size_t query_cap = 0;
+  Grown d_query;                     // staging of the host-pointer collision queries (rcsh_collision_query / rcsh_motion_query) and of the peek's action
   // the environments' collision guard (guard_team.h; rcsh_env_configure_guard): its settings, and two records of [result | t_contact |
   // blocked | hold] -- the last guarded step's (rcsh_env_guard_last) and the scratch of rcsh_env_guard_peek
   struct GuardCfg { bool configured = false, enabled = false, block_undecided = true, truncate = true; int kinds = 0; double resolution = 0; } guard;
@@ -132,20 +156,14 @@ struct rcsh_sim {
   double* d_wframes = nullptr;  // world frames of the shapes + camera per environment (k_shape_frames)
   bool render_f64 = false;      // the ray caster's arithmetic type (rcsh_sim_set_render_f64; RCSH_RENDER_F64=1 at creation)
   std::vector<RenderCam> cams;
-  void* d_image = nullptr;  // staging for the host-pointer render call
-  size_t image_cap = 0;  // device copy of {box, task} (scenes with a free box)
+  Grown d_image;  // staging for the host-pointer render call
   double* pending_task = nullptr;  // task output of the env-step being enqueued (rcsh_env_step_task*)
-  // staging for the host-pointer entry points
-  double* d_stage = nullptr;   // n * kStageWidth doubles
-  double* d_stage2 = nullptr;  // n * 32 doubles
-  // host-buffer env.step / env.reset: page-locked memory between the caller's arrays and the device (a copy to or from pageable memory is
-  // staged by the runtime and waited for, one array at a time: 0.19 of the call's 0.32 ms)
-  char* h_pin = nullptr;
-  size_t h_pin_bytes = 0;
-  uint8_t* d_bytes = nullptr;  // n * 16 bytes
-  uint8_t* d_mask = nullptr;   // n bytes
-  int32_t* d_ints = nullptr;   // n ints
-  float* d_floats = nullptr;   // n floats
+  // staging for the host-pointer entry points: the device side, fixed at creation (stage_create), and page-locked memory between it and
+  // the caller's arrays for the env layer's host forms (PinLayout; a copy to or from pageable memory is staged by the runtime and waited
+  // for, one array at a time: 0.19 of rcsh_env_step's 0.32 ms)
+  Staging stage;
+  PinLayout pin{};
+  Grown h_pin;
   // multi-GPU exchange (RCCL, loaded on first use)
   void* comm = nullptr;            // ncclComm_t
   hipStream_t comm_stream = nullptr;
@@ -753,27 +771,94 @@ int field_of(rcsh_sim* s, const char* name) {
   });
 }
 
+// ---- staging of the host-pointer entry points
+constexpr int kStageWidth = 48;  // doubles per environment of the widest field group (the free body's state)
+constexpr int kInfoBytes = 8, kPoseWidth = 7, kTaskWidth = 9, kObsBase = 14;  // info row; pose; task row = box pose + reward + terminated; observation = kObsBase + narm
+static_assert(kBoxState <= kStageWidth, "the free body's state passes through the staging buffer in one piece");
+static_assert(kPoseWidth <= kTaskWidth, "the box pose comes in through the task rows' slice");
+static_assert(kPoseWidth <= kObsBase, "a forward-kinematics pose goes out through the observations' slice");
+
+int action_width(int mode, int narm) { return mode == RCSH_MODE_JOINTS ? narm : (mode == RCSH_MODE_CARTESIAN_TRPY ? 6 : kPoseWidth); }
+
+int fits(int width, int slice_width, const char* what) {
+  if (width < 0 || width > slice_width) return fail(RCSH_ERR_ARG, std::string(what) + ": wider than its staging slice");
+  return RCSH_OK;
+}
+
+// one buffer, grown on demand: the stream may still be reading or writing the old one
+int grow(rcsh_sim* s, Grown& g, size_t bytes, bool pinned) {
+  if (bytes <= g.cap) return RCSH_OK;
+  if (g.p) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    void* old = g.p;
+    g = Grown{};
+    HIP_TRY(pinned ? hipHostFree(old) : hipFree(old));
+  }
+  void* p = nullptr;
+  HIP_TRY(pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes));
+  g.p = p; g.cap = bytes;
+  return RCSH_OK;
+}
+int grow_device(rcsh_sim* s, Grown& g, size_t bytes) { return grow(s, g, bytes, false); }
+int grow_pinned(rcsh_sim* s, Grown& g, size_t bytes) { return grow(s, g, bytes, true); }
+
+// The device staging's layout: every slice's place and width is decided here, from n and the model's widths.  Called twice: without
+// a base for the size, then with the allocation.
+size_t stage_layout(Staging& st, size_t n, uintptr_t base) {
+  size_t o = 0;
+  auto take = [&](auto*& p, size_t count) {
+    p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + o);
+    o += (count * sizeof(*p) + 255) & ~size_t(255);
+  };
+  take(st.mask, n); take(st.inv_mask, n); take(st.info, n * kInfoBytes); take(st.flag, n); take(st.substeps, n);
+  take(st.grip_cmd, n); take(st.grip_width, n); take(st.action, n * st.action_w); take(st.box_task, n * kTaskWidth);
+  take(st.obs, n * st.obs_w); take(st.wide, n * kStageWidth); take(st.pose, n * kPoseWidth); take(st.q0, n * st.q0_w);
+  take(st.tcp, kPoseWidth);
+  return o;
+}
+int stage_create(rcsh_sim* s) {
+  Staging& st = s->stage;
+  const size_t n = (size_t)s->n;
+  for (int mode = RCSH_MODE_JOINTS; mode <= RCSH_MODE_CARTESIAN_TQUAT; ++mode) st.action_w = std::max(st.action_w, action_width(mode, s->narm));
+  st.obs_w = kObsBase + s->narm;
+  st.q0_w = s->narm;
+  if (s->nl > st.obs_w) return fail(RCSH_ERR_MODEL, "the inverse kinematics' output (nq wide) does not fit the observations' staging slice");
+  HIP_TRY(hipMalloc(&st.base, stage_layout(st, n, 0)));
+  stage_layout(st, n, reinterpret_cast<uintptr_t>(st.base));
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 63) & ~size_t(63); return at; };
+  PinLayout& L = s->pin;
+  L.action = take(sizeof(double) * n * st.action_w);
+  L.gripper = take(sizeof(float) * n);
+  L.box = take(sizeof(double) * n * kPoseWidth);
+  L.obs = take(sizeof(double) * n * st.obs_w);
+  L.info = take(n * kInfoBytes);
+  L.gw = take(sizeof(double) * n);
+  L.sub = take(sizeof(int32_t) * n);
+  L.task = take(sizeof(double) * n * kTaskWidth);
+  L.total = o;
+  return RCSH_OK;
+}
+
 int upload_mask(rcsh_sim* s, const uint8_t* mask, const uint8_t** dev) {
   *dev = nullptr;
   if (!mask) return RCSH_OK;
-  HIP_TRY(hipMemcpyAsync(s->d_mask, mask, s->n, hipMemcpyHostToDevice, s->stream));
-  *dev = s->d_mask;
+  HIP_TRY(hipMemcpyAsync(s->stage.mask, mask, s->n, hipMemcpyHostToDevice, s->stream));
+  *dev = s->stage.mask;
   return RCSH_OK;
 }
 
 // host [n][width] -> state fields
-constexpr int kStageWidth = 48;  // doubles per environment of the staging buffer (the widest field group: the free body's state)
-static_assert(kBoxState <= kStageWidth, "the free body's state passes through the staging buffer in one piece");
 int scatter_host(rcsh_sim* s, int field0, int width, const double* src, const uint8_t* mask) {
   if (width > kStageWidth) return fail(RCSH_ERR_ARG, "scatter_host: field group wider than the staging buffer");
   const uint8_t* dm = nullptr;
   int rc = upload_mask(s, mask, &dm);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(s->d_stage, src, sizeof(double) * s->n * width, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->stage.wide, src, sizeof(double) * s->n * width, hipMemcpyHostToDevice, s->stream));
   // (a write into the state from outside the stepping launches -- set_joints_hard, mjData.qpos = ... -- may move the robot: the gaps the
   // contact check and the contact phase remember for the old position are void; zero = "look at everything")
   if (s->d_slack) HIP_TRY(hipMemsetAsync(s->d_slack, 0, sizeof(float) * (size_t)kSlackStride * s->n, s->stream));
-  hipLaunchKernelGGL(k_scatter, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->S, s->n, field0, width, s->d_stage, dm);
+  hipLaunchKernelGGL(k_scatter, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->S, s->n, field0, width, s->stage.wide, dm);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RCSH_OK;
@@ -781,18 +866,18 @@ int scatter_host(rcsh_sim* s, int field0, int width, const double* src, const ui
 
 int gather_host(rcsh_sim* s, int field0, int width, double* dst) {
   if (width > kStageWidth) return fail(RCSH_ERR_ARG, "gather_host: field group wider than the staging buffer");
-  hipLaunchKernelGGL(k_gather, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, (const double*)s->S, s->n, field0, width, s->d_stage);
+  hipLaunchKernelGGL(k_gather, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, (const double*)s->S, s->n, field0, width, s->stage.wide);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(dst, s->d_stage, sizeof(double) * s->n * width, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(dst, s->stage.wide, sizeof(double) * s->n * width, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RCSH_OK;
 }
 
 int flag_host(rcsh_sim* s, uint32_t bit, uint8_t* dst) {
   if (!dst) return RCSH_OK;
-  hipLaunchKernelGGL(k_flags_to_bytes, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, (const uint32_t*)s->flags, s->n, bit, s->d_bytes);
+  hipLaunchKernelGGL(k_flags_to_bytes, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, (const uint32_t*)s->flags, s->n, bit, s->stage.flag);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(dst, s->d_bytes, s->n, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(dst, s->stage.flag, s->n, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RCSH_OK;
 }
@@ -810,7 +895,7 @@ int flags_update_host(rcsh_sim* s, uint32_t set, uint32_t clear, const uint8_t* 
 }
 
 // Host-buffer env.reset(mask): the reset launch writes observation / info / gripper width of the masked environments only,
-// the rows of the others in the shared staging buffers would be whatever an earlier call left there.  An observation-only
+// the rows of the others in the staging slices would be whatever an earlier call left there.  An observation-only
 // pass (no stepping) over the complement fills them with the environments' current observation.
 int observe_unmasked(rcsh_sim* s, const uint8_t* mask) {
   if (!mask) return RCSH_OK;
@@ -818,16 +903,64 @@ int observe_unmasked(rcsh_sim* s, const uint8_t* mask) {
   bool any = false;
   for (int e = 0; e < s->n; ++e) { inv[e] = !mask[e]; any = any || inv[e]; }
   if (!any) return RCSH_OK;
-  uint8_t* d_inv = s->d_bytes + (size_t)s->n * 8;  // (info occupies the first 8 n bytes)
-  HIP_TRY(hipMemcpyAsync(d_inv, inv.data(), s->n, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->stage.inv_mask, inv.data(), s->n, hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));  // `inv` goes out of scope
   RunOp op{};
   op.nsteps = 0;
   op.write_obs = 1;
   op.observe_only = 1;  // the frames the reset launch just recorded for the masked environments stay pending (rend.count / last)
-  op.mask = d_inv;
-  op.obs = s->d_stage2; op.info = s->d_bytes; op.gripper_width = s->d_stage;
+  op.mask = s->stage.inv_mask;
+  op.obs = s->stage.obs; op.info = s->stage.info; op.gripper_width = s->stage.grip_width;
   return launch_run(s, op, false);
+}
+
+size_t align8(size_t x) { return (x + 7) & ~(size_t)7; }
+// a record of the collision guard (rcsh_sim::d_guard holds two, h_guard the front of one): [t_contact | result | blocked | hold]
+struct GuardLayout { size_t t_contact, result, blocked, hold, host_bytes, bytes; };  // host_bytes: up to the end of `blocked`, what a host copy takes
+GuardLayout guard_layout(const rcsh_sim* s) {
+  const size_t n = (size_t)s->n;
+  GuardLayout G{};
+  G.result = G.t_contact + align8(8 * n);
+  G.blocked = G.result + align8(4 * n);
+  G.hold = G.blocked + align8(n);
+  G.host_bytes = G.blocked + n;
+  G.bytes = G.hold + align8(n);
+  return G;
+}
+
+// the page-locked buffer (laid out by rcsh_sim::pin), allocated at its first use
+int pin_ready(rcsh_sim* s, char*& h) {
+  int rc = grow_pinned(s, s->h_pin, s->pin.total);
+  h = static_cast<char*>(s->h_pin.p);
+  return rc;
+}
+// host array -> page-locked memory -> device slice, enqueued (the entry point's closing wait covers it)
+int pin_upload(rcsh_sim* s, void* dev, char* pinned, const void* src, size_t bytes) {
+  std::memcpy(pinned, src, bytes);
+  HIP_TRY(hipMemcpyAsync(dev, pinned, bytes, hipMemcpyHostToDevice, s->stream));
+  return RCSH_OK;
+}
+// How the env layer's host forms end: the requested outputs go from their slices to page-locked memory -- with the last guarded step's
+// record, if asked: rcsh_env_guard_last then needs no wait of its own --, ONE wait, and out to the caller's arrays.
+struct EnvOut { double* obs; uint8_t* info; double* gw; int32_t* substeps; double* task; };
+int fetch_env_outputs(rcsh_sim* s, const EnvOut& out, bool guard_record_too) {
+  const PinLayout& L = s->pin;
+  char* h = nullptr;
+  int rc = pin_ready(s, h);
+  if (rc) return rc;
+  const Staging& st = s->stage;
+  const size_t n = (size_t)s->n;
+  const struct { void* dst; const void* src; size_t at, bytes; } pieces[] = {
+      {out.obs, st.obs, L.obs, sizeof(double) * n * st.obs_w}, {out.info, st.info, L.info, n * kInfoBytes},
+      {out.gw, st.grip_width, L.gw, sizeof(double) * n},       {out.substeps, st.substeps, L.sub, sizeof(int32_t) * n},
+      {out.task, st.box_task, L.task, sizeof(double) * n * kTaskWidth}};
+  for (const auto& p : pieces)
+    if (p.dst) HIP_TRY(hipMemcpyAsync(h + p.at, p.src, p.bytes, hipMemcpyDeviceToHost, s->stream));
+  if (guard_record_too) HIP_TRY(hipMemcpyAsync(s->h_guard, s->d_guard, guard_layout(s).host_bytes, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  for (const auto& p : pieces)
+    if (p.dst) std::memcpy(p.dst, h + p.at, p.bytes);
+  return RCSH_OK;
 }
 
 std::vector<double> tile(const double* row, int width, int n) {
@@ -910,12 +1043,7 @@ int rcsh_sim_create(const rcsh_model_desc* model, int32_t n_envs, int32_t device
   HIP_NEW(hipMalloc(&s->S, sizeof(double) * n * s->nfields));
   HIP_NEW(hipMalloc(&s->flags, sizeof(uint32_t) * n));
   HIP_NEW(hipMalloc(&s->conv, sizeof(int32_t) * n));
-  HIP_NEW(hipMalloc(&s->d_stage, sizeof(double) * n * kStageWidth));
-  HIP_NEW(hipMalloc(&s->d_stage2, sizeof(double) * n * 32));
-  HIP_NEW(hipMalloc(&s->d_bytes, n * 16));
-  HIP_NEW(hipMalloc(&s->d_mask, n));
-  HIP_NEW(hipMalloc(&s->d_ints, sizeof(int32_t) * n));
-  HIP_NEW(hipMalloc(&s->d_floats, sizeof(float) * n));
+  if (int rc = stage_create(s)) return cleanup(rc, g_err);
   HIP_NEW(hipMemsetAsync(s->S, 0, sizeof(double) * n * s->nfields, s->stream));
   HIP_NEW(hipMemsetAsync(s->conv, 0, sizeof(int32_t) * n, s->stream));
   // Sim::converged starts true (reference src/sim/sim.h:70); SimRobotState.ik_success starts true
@@ -951,15 +1079,15 @@ void rcsh_sim_destroy(rcsh_sim* s) {
   hipFree(s->d_model); hipFree(s->d_coll_xyzr); hipFree(s->d_coll_cls); hipFree(s->S); hipFree(s->flags); hipFree(s->conv);
   hipFree(s->d_cgeoms); hipFree(s->d_cverts); hipFree(s->d_pairs); hipFree(s->d_chk_geoms); hipFree(s->d_chk_ent); hipFree(s->d_lev);
   hipFree(s->d_slack);
-  hipFree(s->d_query);
+  hipFree(s->d_query.p);
   hipFree(s->d_guard);
   if (s->h_guard) hipHostFree(s->h_guard);
   hipFree(s->d_esc); hipFree(s->d_esc_ctr); hipFree(s->d_snap); hipFree(s->d_snap_flags); hipFree(s->d_snap_conv);
   hipFree(s->rend.last); hipFree(s->rend.snap); hipFree(s->rend.count);
-  hipFree(s->d_boxtask); hipFree(s->d_rshapes); hipFree(s->d_rplanes); hipFree(s->d_rcolours); hipFree(s->d_frames); hipFree(s->d_wframes); hipFree(s->d_image);
+  hipFree(s->d_boxtask); hipFree(s->d_rshapes); hipFree(s->d_rplanes); hipFree(s->d_rcolours); hipFree(s->d_frames); hipFree(s->d_wframes); hipFree(s->d_image.p);
   hipFree(s->d_redge_planes); hipFree(s->d_redge_verts); hipFree(s->d_rviews);
-  if (s->h_pin) hipHostFree(s->h_pin);
-  hipFree(s->d_stage); hipFree(s->d_stage2); hipFree(s->d_bytes); hipFree(s->d_mask); hipFree(s->d_ints); hipFree(s->d_floats);
+  if (s->h_pin.p) hipHostFree(s->h_pin.p);
+  hipFree(s->stage.base);
   if (s->own_stream) hipStreamDestroy(s->own_stream);
   delete s;
 }
@@ -1019,7 +1147,6 @@ int rcsh_sim_get_config(const rcsh_sim* s, int32_t* a, int32_t* r, int32_t* f, i
 int rcsh_sim_step(rcsh_sim* s, int64_t k) {
   REQUIRE_SIM(s);
   if (k < 0) return fail(RCSH_ERR_ARG, "step count must be non-negative");
-  HIP_TRY(hipSetDevice(s->device));
   RunOp op{};
   op.nsteps = (int32_t)k;
   int rc = launch_run(s, op, false);
@@ -1030,7 +1157,6 @@ int rcsh_sim_step(rcsh_sim* s, int64_t k) {
 
 int rcsh_sim_step_until_convergence(rcsh_sim* s) {
   REQUIRE_SIM(s);
-  HIP_TRY(hipSetDevice(s->device));
   RunOp op{};
   op.nsteps = -1;
   int rc = launch_run(s, op, false);
@@ -1183,19 +1309,20 @@ int rcsh_robot_get_joint_position(rcsh_sim* s, double* q) {
 
 int rcsh_robot_get_cartesian_position(rcsh_sim* s, double* pose) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
-  HIP_TRY(hipSetDevice(s->device));
   RunOp op{};
   op.nsteps = 0;
   op.write_obs = 1;
   op.observe_only = 1;
-  op.obs = s->d_stage2;
+  op.obs = s->stage.obs;
   int rc = launch_run(s, op, false);
   if (rc) return rc;
-  const int ow = 14 + s->narm;
-  std::vector<double> obs((size_t)s->n * ow);
-  HIP_TRY(hipMemcpyAsync(obs.data(), s->d_stage2, sizeof(double) * obs.size(), hipMemcpyDeviceToHost, s->stream));
+  char* h = nullptr;
+  if ((rc = pin_ready(s, h))) return rc;
+  h += s->pin.obs;
+  const size_t ow = (size_t)s->stage.obs_w;
+  HIP_TRY(hipMemcpyAsync(h, s->stage.obs, sizeof(double) * s->n * ow, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
-  for (int e = 0; e < s->n; ++e) std::memcpy(pose + 7 * e, &obs[(size_t)e * ow], 7 * sizeof(double));
+  for (int e = 0; e < s->n; ++e) std::memcpy(pose + kPoseWidth * e, h + sizeof(double) * e * ow, kPoseWidth * sizeof(double));  // (an observation begins with the pose)
   return RCSH_OK;
 }
 
@@ -1227,15 +1354,14 @@ int launch_cartesian(rcsh_sim* s, const CartOp& op) {
 int rcsh_robot_set_cartesian_position(rcsh_sim* s, const double* pose, const uint8_t* mask) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!pose) return fail(RCSH_ERR_ARG, "null pose");
-  HIP_TRY(hipSetDevice(s->device));
   const uint8_t* dm = nullptr;
   int rc = upload_mask(s, mask, &dm);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(s->d_stage, pose, sizeof(double) * s->n * 7, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->stage.pose, pose, sizeof(double) * s->n * kPoseWidth, hipMemcpyHostToDevice, s->stream));
   CartOp op{};
   op.env_layer = 0;
   op.mask = dm;
-  op.action = s->d_stage;
+  op.action = s->stage.pose;
   rc = launch_cartesian(s, op);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1245,31 +1371,31 @@ int rcsh_robot_set_cartesian_position(rcsh_sim* s, const double* pose, const uin
 namespace {
 int run_ik(rcsh_sim* s, const double* pose, const double* q0, const double* tcp7, double* out, int out_width, uint8_t* success,
            int32_t* iterations, int forward) {
-  HIP_TRY(hipSetDevice(s->device));
   const size_t n = s->n;
-  double* d_pose = s->d_stage;            // n*7
-  double* d_q0 = s->d_stage + n * 8;      // n*narm
-  double* d_tcp = s->d_stage + n * 16;    // 7
-  double* d_out = s->d_stage2;            // n*out_width
-  if (pose) HIP_TRY(hipMemcpyAsync(d_pose, pose, sizeof(double) * n * 7, hipMemcpyHostToDevice, s->stream));
+  const Staging& st = s->stage;
+  int rc = fits(s->narm, st.q0_w, "the IK's start configuration");
+  if (!rc) rc = fits(out_width, st.obs_w, "the IK's output");
+  if (rc) return rc;
+  double *d_pose = st.pose, *d_q0 = st.q0, *d_tcp = st.tcp, *d_out = st.obs;
+  if (pose) HIP_TRY(hipMemcpyAsync(d_pose, pose, sizeof(double) * n * kPoseWidth, hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipMemcpyAsync(d_q0, q0, sizeof(double) * n * s->narm, hipMemcpyHostToDevice, s->stream));
-  if (tcp7) HIP_TRY(hipMemcpyAsync(d_tcp, tcp7, sizeof(double) * 7, hipMemcpyHostToDevice, s->stream));
+  if (tcp7) HIP_TRY(hipMemcpyAsync(d_tcp, tcp7, sizeof(double) * kPoseWidth, hipMemcpyHostToDevice, s->stream));
   Params P = make_params(s);
   hipError_t err = hipSuccess;
   dispatch_topology(s->narm, s->grip, [&](auto topo) {
     using T = decltype(topo);
     if (forward)
       hipLaunchKernelGGL(k_ik<T>, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, P, (const double*)d_pose, (const double*)d_q0,
-                         tcp7 ? (const double*)d_tcp : (const double*)nullptr, d_out, s->d_bytes, s->d_ints, forward);
+                         tcp7 ? (const double*)d_tcp : (const double*)nullptr, d_out, st.flag, st.substeps, forward);
     else
       hipLaunchKernelGGL(k_ik_team<T>, dim3((s->n + 3) / 4), dim3(64), 0, s->stream, P, (const double*)d_pose, (const double*)d_q0,
-                         tcp7 ? (const double*)d_tcp : (const double*)nullptr, d_out, s->d_bytes, s->d_ints);
+                         tcp7 ? (const double*)d_tcp : (const double*)nullptr, d_out, st.flag, st.substeps);
     err = hipGetLastError();
   });
   if (err != hipSuccess) return fail(RCSH_ERR_DEVICE, std::string("k_ik launch: ") + hipGetErrorString(err));
   HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * n * out_width, hipMemcpyDeviceToHost, s->stream));
-  if (success) HIP_TRY(hipMemcpyAsync(success, s->d_bytes, n, hipMemcpyDeviceToHost, s->stream));
-  if (iterations) HIP_TRY(hipMemcpyAsync(iterations, s->d_ints, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
+  if (success) HIP_TRY(hipMemcpyAsync(success, st.flag, n, hipMemcpyDeviceToHost, s->stream));
+  if (iterations) HIP_TRY(hipMemcpyAsync(iterations, st.substeps, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RCSH_OK;
 }
@@ -1284,7 +1410,7 @@ int rcsh_ik_inverse(rcsh_sim* s, const double* pose, const double* q0, const dou
 int rcsh_ik_forward(rcsh_sim* s, const double* q0, const double* tcp7, double* pose) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!q0 || !pose) return fail(RCSH_ERR_ARG, "null argument");
-  return run_ik(s, nullptr, q0, tcp7, pose, 7, nullptr, nullptr, 1);
+  return run_ik(s, nullptr, q0, tcp7, pose, kPoseWidth, nullptr, nullptr, 1);
 }
 
 // ---- collision queries on caller-supplied configurations (csrc/query_team.h)
@@ -1380,14 +1506,6 @@ int motion_query_dev(rcsh_sim* s, const double* q_from, const double* q_to, cons
   A.q0 = q_from; A.q1 = q_to; A.free_qpos = free_qpos; A.resolution = resolution; A.result = result; A.t_contact = t_contact;
   return query_launch(s, A, true);
 }
-int query_stage(rcsh_sim* s, size_t bytes) {
-  if (bytes <= s->query_cap) return RCSH_OK;
-  if (s->d_query) { HIP_TRY(hipStreamSynchronize(s->stream)); HIP_TRY(hipFree(s->d_query)); s->d_query = nullptr; s->query_cap = 0; }
-  HIP_TRY(hipMalloc(&s->d_query, bytes));
-  s->query_cap = bytes;
-  return RCSH_OK;
-}
-size_t align8(size_t x) { return (x + 7) & ~(size_t)7; }
 }  // namespace
 
 int rcsh_collision_query(rcsh_sim* s, const double* q, const double* free_qpos, int32_t m, int32_t kinds, uint8_t* hit, uint8_t* kinds_hit,
@@ -1401,8 +1519,8 @@ int rcsh_collision_query(rcsh_sim* s, const double* q, const double* free_qpos, 
   if ((rc = query_finite(q, n * nl, "q"))) return rc;
   if (free_qpos && (rc = query_finite(free_qpos, n * 7, "free_qpos"))) return rc;
   const size_t oq = 0, of = oq + 8 * n * nl, oh = of + (free_qpos ? 8 * n * 7 : 0), ok = align8(oh + n), op = align8(ok + n), end = op + 8 * n;
-  if ((rc = query_stage(s, end))) return rc;
-  char* d = static_cast<char*>(s->d_query);
+  if ((rc = grow_device(s, s->d_query, end))) return rc;
+  char* d = static_cast<char*>(s->d_query.p);
   HIP_TRY(hipMemcpyAsync(d + oq, q, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
   if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
   rc = point_query_dev(s, reinterpret_cast<const double*>(d + oq), free_qpos ? reinterpret_cast<const double*>(d + of) : nullptr, m, kinds,
@@ -1435,8 +1553,8 @@ int rcsh_motion_query(rcsh_sim* s, const double* q_from, const double* q_to, con
   if ((rc = query_finite(q_from, n * nl, "q_from")) || (rc = query_finite(q_to, n * nl, "q_to"))) return rc;
   if (free_qpos && (rc = query_finite(free_qpos, n * 7, "free_qpos"))) return rc;
   const size_t oa = 0, ob = oa + 8 * n * nl, of = ob + 8 * n * nl, orr = of + (free_qpos ? 8 * n * 7 : 0), ot = orr + 8 * n, end = ot + 8 * n;
-  if ((rc = query_stage(s, end))) return rc;
-  char* d = static_cast<char*>(s->d_query);
+  if ((rc = grow_device(s, s->d_query, end))) return rc;
+  char* d = static_cast<char*>(s->d_query.p);
   HIP_TRY(hipMemcpyAsync(d + oa, q_from, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipMemcpyAsync(d + ob, q_to, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
   if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
@@ -1634,7 +1752,6 @@ int rcsh_sim_add_free_box(rcsh_sim* s, const rcsh_free_box_desc* d) {
   b.scale = 1.0 / (meaninertia * nv);
   b.noslip_tolerance = d->noslip_tolerance;
   s->box = b;
-  HIP_TRY(hipSetDevice(s->device));
   if (int rc = upload_boxtask(s)) return rc;
   if (int rc = upload_contact_table(s)) return rc;
   return rcsh_sim_reset_free_box(s);
@@ -1779,7 +1896,6 @@ size_t rcsh_sim_state_bytes(const rcsh_sim* s) {
 int rcsh_sim_get_state(rcsh_sim* s, void* blob) {
   REQUIRE_SIM(s);
   if (!blob) return fail(RCSH_ERR_ARG, "null state blob");
-  HIP_TRY(hipSetDevice(s->device));
   char* b = static_cast<char*>(blob);
   {
     const uint32_t hn = (uint32_t)s->n, hf = (uint32_t)s->nfields;
@@ -1799,7 +1915,6 @@ int rcsh_sim_get_state(rcsh_sim* s, void* blob) {
 int rcsh_sim_set_state(rcsh_sim* s, const void* blob) {
   REQUIRE_SIM(s);
   if (!blob) return fail(RCSH_ERR_ARG, "null state blob");
-  HIP_TRY(hipSetDevice(s->device));
   const char* b = static_cast<const char*>(blob);
   {
     uint32_t hn = 0, hf = 0;
@@ -1848,16 +1963,15 @@ int rcsh_env_configure(rcsh_sim* s, const rcsh_env_desc* env) {
   return RCSH_OK;
 }
 
-int rcsh_env_obs_width(const rcsh_sim* s) { return s ? 14 + s->narm : 0; }
+int rcsh_env_obs_width(const rcsh_sim* s) { return s ? kObsBase + s->narm : 0; }
 int rcsh_env_action_width(const rcsh_sim* s) {
   if (!s) return 0;
-  return s->env.mode == RCSH_MODE_JOINTS ? s->narm : (s->env.mode == RCSH_MODE_CARTESIAN_TRPY ? 6 : 7);
+  return action_width(s->env.mode, s->narm);
 }
 
 int rcsh_env_reset_dev(rcsh_sim* s, const uint8_t* mask_dev, double* obs_dev, uint8_t* info_dev, double* gw_dev) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!s->env_configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure first");
-  HIP_TRY(hipSetDevice(s->device));
   RunOp op{};
   op.do_reset = 1;
   op.nsteps = 1;
@@ -1870,15 +1984,14 @@ int rcsh_env_reset_dev(rcsh_sim* s, const uint8_t* mask_dev, double* obs_dev, ui
 // ---- the collision guard (csrc/guard_team.h)
 namespace {
 struct GuardRecord { int32_t* result; double* t_contact; uint8_t* blocked; uint8_t* hold; };
-size_t guard_record_bytes(const rcsh_sim* s) { return align8(8 * (size_t)s->n) + align8(4 * (size_t)s->n) + 2 * align8((size_t)s->n); }
 GuardRecord guard_record(const rcsh_sim* s, int which) {  // 0: the last guarded step, 1: the peek's scratch
-  char* d = static_cast<char*>(s->d_guard) + (size_t)which * guard_record_bytes(s);
-  const size_t n = (size_t)s->n;
+  const GuardLayout G = guard_layout(s);
+  char* d = static_cast<char*>(s->d_guard) + (size_t)which * G.bytes;
   GuardRecord r{};
-  r.t_contact = reinterpret_cast<double*>(d);
-  r.result = reinterpret_cast<int32_t*>(d + align8(8 * n));
-  r.blocked = reinterpret_cast<uint8_t*>(d + align8(8 * n) + align8(4 * n));
-  r.hold = r.blocked + align8(n);
+  r.t_contact = reinterpret_cast<double*>(d + G.t_contact);
+  r.result = reinterpret_cast<int32_t*>(d + G.result);
+  r.blocked = reinterpret_cast<uint8_t*>(d + G.blocked);
+  r.hold = reinterpret_cast<uint8_t*>(d + G.hold);
   return r;
 }
 __global__ void k_guard_fill(int32_t* result, double* t_contact, uint8_t* blocked, uint8_t* hold, int n) {
@@ -1938,9 +2051,8 @@ int rcsh_env_configure_guard(rcsh_sim* s, const rcsh_guard_desc* g) {
     return fail(RCSH_ERR_STATE, "the collision guard guards joint-space actions only: the environments are configured for a Cartesian control mode");
   int rc = query_check(s, s->n, g->kinds, nullptr);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  if (!s->d_guard) HIP_TRY(hipMalloc(&s->d_guard, 2 * guard_record_bytes(s)));
-  if (!s->h_guard) { void* p = nullptr; HIP_TRY(hipHostMalloc(&p, guard_record_bytes(s), hipHostMallocDefault)); s->h_guard = (char*)p; }
+  if (!s->d_guard) HIP_TRY(hipMalloc(&s->d_guard, 2 * guard_layout(s).bytes));
+  if (!s->h_guard) { void* p = nullptr; HIP_TRY(hipHostMalloc(&p, guard_layout(s).host_bytes, hipHostMallocDefault)); s->h_guard = (char*)p; }
   s->guard.configured = true;
   s->guard.enabled = g->enabled != 0;
   s->guard.kinds = g->kinds;
@@ -1955,7 +2067,6 @@ int rcsh_env_guard_peek_dev(rcsh_sim* s, const double* action_dev, int32_t* resu
   if (!s->guard.configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure_guard first");
   if (s->env.mode != RCSH_MODE_JOINTS) return fail(RCSH_ERR_STATE, "the collision guard answers for joint-space actions only: the environments are configured for a Cartesian control mode");
   if (!action_dev || !result_dev || !t_contact_dev || !blocked_dev) return fail(RCSH_ERR_ARG, "null argument");
-  HIP_TRY(hipSetDevice(s->device));
   return guard_launch(s, action_dev, result_dev, t_contact_dev, blocked_dev, nullptr);
 }
 
@@ -1967,9 +2078,8 @@ int rcsh_env_guard_peek(rcsh_sim* s, const double* action, int32_t* result, doub
   const size_t n = (size_t)s->n, na = n * (size_t)s->narm;
   int rc = query_finite(action, na, "action");
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  if ((rc = query_stage(s, 8 * na))) return rc;
-  double* d_action = static_cast<double*>(s->d_query);
+  if ((rc = grow_device(s, s->d_query, 8 * na))) return rc;
+  double* d_action = static_cast<double*>(s->d_query.p);
   const GuardRecord r = guard_record(s, 1);
   HIP_TRY(hipMemcpyAsync(d_action, action, 8 * na, hipMemcpyHostToDevice, s->stream));
   if ((rc = guard_launch(s, d_action, r.result, r.t_contact, r.blocked, nullptr))) return rc;
@@ -1995,13 +2105,13 @@ int rcsh_env_guard_last(rcsh_sim* s, int32_t* result, double* t_contact, uint8_t
   if (!s->guard.configured || !s->guard_stepped) return fail(RCSH_ERR_STATE, "no guarded step has run");
   const size_t n = (size_t)s->n;
   if (s->guard_host_valid) {  // (rcsh_env_step brought the record along with its outputs)
+    const GuardLayout G = guard_layout(s);
     const char* hg = s->h_guard;
-    if (t_contact) std::memcpy(t_contact, hg, 8 * n);
-    if (result) std::memcpy(result, hg + align8(8 * n), 4 * n);
-    if (blocked) std::memcpy(blocked, hg + align8(8 * n) + align8(4 * n), n);
+    if (t_contact) std::memcpy(t_contact, hg + G.t_contact, 8 * n);
+    if (result) std::memcpy(result, hg + G.result, 4 * n);
+    if (blocked) std::memcpy(blocked, hg + G.blocked, n);
     return RCSH_OK;
   }
-  HIP_TRY(hipSetDevice(s->device));
   const GuardRecord r = guard_record(s, 0);
   if (result) HIP_TRY(hipMemcpyAsync(result, r.result, 4 * n, hipMemcpyDeviceToHost, s->stream));
   if (t_contact) HIP_TRY(hipMemcpyAsync(t_contact, r.t_contact, 8 * n, hipMemcpyDeviceToHost, s->stream));
@@ -2015,7 +2125,6 @@ int rcsh_env_step_dev(rcsh_sim* s, const double* action_dev, const float* grippe
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!s->env_configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure first");
   if (!action_dev) return fail(RCSH_ERR_ARG, "null action");
-  HIP_TRY(hipSetDevice(s->device));
   RunOp op{};
   op.apply_action = 1;
   const bool guarded = s->guard.enabled && s->env.mode == RCSH_MODE_JOINTS;  // (rcsh_env_configure refuses a Cartesian mode under a guard)
@@ -2063,7 +2172,6 @@ int rcsh_env_configure_pick_task(rcsh_sim* s, const rcsh_pick_task_desc* t) {
   s->task.pick_cube = 1;
   for (int k = 0; k < 3; ++k) s->task.ee_home[k] = t->ee_home[k];
   s->task.success_z = t->success_height;
-  HIP_TRY(hipSetDevice(s->device));
   return upload_boxtask(s);
 }
 
@@ -2073,7 +2181,6 @@ int rcsh_env_reset_task_dev(rcsh_sim* s, const uint8_t* mask_dev, const double* 
   if (!s->env_configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure first");
   if (!s->task.pick_cube) return fail(RCSH_ERR_STATE, "call rcsh_env_configure_pick_task first");
   if (!box_qpos_dev) return fail(RCSH_ERR_ARG, "null box pose");
-  HIP_TRY(hipSetDevice(s->device));
   RunOp op{};
   op.do_reset = 1;
   op.nsteps = 1;
@@ -2094,119 +2201,70 @@ int rcsh_env_step_task_dev(rcsh_sim* s, const double* action_dev, const float* g
   return rc;
 }
 
-int rcsh_env_reset_task(rcsh_sim* s, const uint8_t* mask, const double* box_qpos, double* obs, uint8_t* info, double* gw) {
-  REQUIRE_SIM(s);
-  if (!box_qpos) return fail(RCSH_ERR_ARG, "null box pose");
+namespace {
+// the host forms of env.reset: with the box pose of the pick-up task's reset, or without
+int env_reset_host(rcsh_sim* s, const uint8_t* mask, const double* box_qpos, double* obs, uint8_t* info, double* gw) {
+  const Staging& st = s->stage;
   const uint8_t* dm = nullptr;
   int rc = upload_mask(s, mask, &dm);
   if (rc) return rc;
-  double* d_box = s->d_stage + (size_t)s->n * 16;
-  HIP_TRY(hipMemcpyAsync(d_box, box_qpos, sizeof(double) * s->n * 7, hipMemcpyHostToDevice, s->stream));
-  rc = rcsh_env_reset_task_dev(s, dm, d_box, s->d_stage2, s->d_bytes, s->d_stage);
+  if (box_qpos) {
+    char* h = nullptr;
+    if ((rc = pin_ready(s, h))) return rc;
+    if ((rc = pin_upload(s, st.box_task, h + s->pin.box, box_qpos, sizeof(double) * s->n * kPoseWidth))) return rc;
+    rc = rcsh_env_reset_task_dev(s, dm, st.box_task, st.obs, st.info, st.grip_width);
+  } else {
+    rc = rcsh_env_reset_dev(s, dm, st.obs, st.info, st.grip_width);
+  }
   if (!rc) rc = observe_unmasked(s, mask);
   if (rc) return rc;
-  const int ow = 14 + s->narm;
-  if (obs) HIP_TRY(hipMemcpyAsync(obs, s->d_stage2, sizeof(double) * s->n * ow, hipMemcpyDeviceToHost, s->stream));
-  if (info) HIP_TRY(hipMemcpyAsync(info, s->d_bytes, (size_t)s->n * 8, hipMemcpyDeviceToHost, s->stream));
-  if (gw) HIP_TRY(hipMemcpyAsync(gw, s->d_stage, sizeof(double) * s->n, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  return fetch_env_outputs(s, EnvOut{obs, info, gw, nullptr, nullptr}, false);
+}
+
+// the host forms of env.step; `with_task`: the pick-up task's rows are written (and fetched into out.task, if given)
+int env_step_host(rcsh_sim* s, const double* action, const float* gripper, const EnvOut& out, bool with_task) {
+  if (!action) return fail(RCSH_ERR_ARG, "null action");
+  const Staging& st = s->stage;
+  const int aw = rcsh_env_action_width(s);
+  const PinLayout& L = s->pin;
+  char* h = nullptr;
+  int rc = fits(aw, st.action_w, "the env-step's action");
+  if (!rc) rc = pin_ready(s, h);
+  if (!rc) rc = pin_upload(s, st.action, h + L.action, action, sizeof(double) * s->n * aw);
+  if (!rc && gripper) rc = pin_upload(s, st.grip_cmd, h + L.gripper, gripper, sizeof(float) * s->n);
+  if (rc) return rc;
+  s->pending_task = with_task ? st.box_task : nullptr;
+  rc = rcsh_env_step_dev(s, st.action, gripper ? st.grip_cmd : nullptr, st.obs, st.info, st.grip_width, st.substeps);
+  s->pending_task = nullptr;
+  if (rc) return rc;
+  const bool guard_record_too = s->guard.enabled && s->guard_stepped && s->h_guard;
+  if ((rc = fetch_env_outputs(s, out, guard_record_too))) return rc;
+  s->guard_host_valid = guard_record_too;
   return RCSH_OK;
+}
+}  // namespace
+
+int rcsh_env_reset_task(rcsh_sim* s, const uint8_t* mask, const double* box_qpos, double* obs, uint8_t* info, double* gw) {
+  REQUIRE_SIM(s);
+  if (!box_qpos) return fail(RCSH_ERR_ARG, "null box pose");
+  return env_reset_host(s, mask, box_qpos, obs, info, gw);
 }
 
 int rcsh_env_step_task(rcsh_sim* s, const double* action, const float* gripper, double* obs, uint8_t* info, double* gw,
                        int32_t* substeps, double* task) {
   REQUIRE_SIM(s);
   if (!s->task.pick_cube) return fail(RCSH_ERR_STATE, "call rcsh_env_configure_pick_task first");
-  double* d_task = s->d_stage + (size_t)s->n * 16;
-  s->pending_task = d_task;
-  int rc = rcsh_env_step(s, action, gripper, obs, info, gw, substeps);
-  s->pending_task = nullptr;
-  if (rc) return rc;
-  if (task) {
-    HIP_TRY(hipMemcpyAsync(task, d_task, sizeof(double) * s->n * 9, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-  }
-  return RCSH_OK;
+  return env_step_host(s, action, gripper, EnvOut{obs, info, gw, substeps, task}, true);
 }
-
-namespace {
-// page-locked staging for the host-buffer entry points: [action | gripper | obs | info | gripper width | substeps]
-struct PinLayout { size_t action, gripper, obs, info, gw, sub, total; };
-PinLayout pin_layout(const rcsh_sim* s, int aw, int ow) {
-  PinLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 63) & ~size_t(63); return at; };
-  L.action = take(sizeof(double) * s->n * aw);
-  L.gripper = take(sizeof(float) * s->n);
-  L.obs = take(sizeof(double) * s->n * ow);
-  L.info = take((size_t)s->n * 8);
-  L.gw = take(sizeof(double) * s->n);
-  L.sub = take(sizeof(int32_t) * s->n);
-  L.total = o;
-  return L;
-}
-int pin_reserve(rcsh_sim* s, size_t bytes) {
-  if (s->h_pin_bytes >= bytes) return RCSH_OK;
-  if (s->h_pin) { HIP_TRY(hipStreamSynchronize(s->stream)); hipHostFree(s->h_pin); s->h_pin = nullptr; s->h_pin_bytes = 0; }
-  void* p = nullptr;
-  HIP_TRY(hipHostMalloc(&p, bytes, hipHostMallocDefault));
-  s->h_pin = (char*)p; s->h_pin_bytes = bytes;
-  return RCSH_OK;
-}
-}  // namespace
 
 int rcsh_env_reset(rcsh_sim* s, const uint8_t* mask, double* obs, uint8_t* info, double* gw) {
   REQUIRE_SIM(s);
-  const uint8_t* dm = nullptr;
-  int rc = upload_mask(s, mask, &dm);
-  if (rc) return rc;
-  rc = rcsh_env_reset_dev(s, dm, s->d_stage2, s->d_bytes, s->d_stage);
-  if (!rc) rc = observe_unmasked(s, mask);
-  if (rc) return rc;
-  const int ow = 14 + s->narm;
-  const PinLayout L = pin_layout(s, rcsh_env_action_width(s), ow);
-  rc = pin_reserve(s, L.total);
-  if (rc) return rc;
-  if (obs) HIP_TRY(hipMemcpyAsync(s->h_pin + L.obs, s->d_stage2, sizeof(double) * s->n * ow, hipMemcpyDeviceToHost, s->stream));
-  if (info) HIP_TRY(hipMemcpyAsync(s->h_pin + L.info, s->d_bytes, (size_t)s->n * 8, hipMemcpyDeviceToHost, s->stream));
-  if (gw) HIP_TRY(hipMemcpyAsync(s->h_pin + L.gw, s->d_stage, sizeof(double) * s->n, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  if (obs) std::memcpy(obs, s->h_pin + L.obs, sizeof(double) * s->n * ow);
-  if (info) std::memcpy(info, s->h_pin + L.info, (size_t)s->n * 8);
-  if (gw) std::memcpy(gw, s->h_pin + L.gw, sizeof(double) * s->n);
-  return RCSH_OK;
+  return env_reset_host(s, mask, nullptr, obs, info, gw);
 }
 
 int rcsh_env_step(rcsh_sim* s, const double* action, const float* gripper, double* obs, uint8_t* info, double* gw, int32_t* substeps) {
   REQUIRE_SIM(s);
-  if (!action) return fail(RCSH_ERR_ARG, "null action");
-  const int aw = rcsh_env_action_width(s), ow = 14 + s->narm;
-  const PinLayout L = pin_layout(s, aw, ow);
-  int rc = pin_reserve(s, L.total);
-  if (rc) return rc;
-  double* d_action = s->d_stage + (size_t)s->n;  // d_stage[0..n) carries gripper widths
-  std::memcpy(s->h_pin + L.action, action, sizeof(double) * s->n * aw);
-  HIP_TRY(hipMemcpyAsync(d_action, s->h_pin + L.action, sizeof(double) * s->n * aw, hipMemcpyHostToDevice, s->stream));
-  if (gripper) {
-    std::memcpy(s->h_pin + L.gripper, gripper, sizeof(float) * s->n);
-    HIP_TRY(hipMemcpyAsync(s->d_floats, s->h_pin + L.gripper, sizeof(float) * s->n, hipMemcpyHostToDevice, s->stream));
-  }
-  rc = rcsh_env_step_dev(s, d_action, gripper ? s->d_floats : nullptr, s->d_stage2, s->d_bytes, s->d_stage, s->d_ints);
-  if (rc) return rc;
-  if (obs) HIP_TRY(hipMemcpyAsync(s->h_pin + L.obs, s->d_stage2, sizeof(double) * s->n * ow, hipMemcpyDeviceToHost, s->stream));
-  if (info) HIP_TRY(hipMemcpyAsync(s->h_pin + L.info, s->d_bytes, (size_t)s->n * 8, hipMemcpyDeviceToHost, s->stream));
-  if (gw) HIP_TRY(hipMemcpyAsync(s->h_pin + L.gw, s->d_stage, sizeof(double) * s->n, hipMemcpyDeviceToHost, s->stream));
-  if (substeps) HIP_TRY(hipMemcpyAsync(s->h_pin + L.sub, s->d_ints, sizeof(int32_t) * s->n, hipMemcpyDeviceToHost, s->stream));
-  const bool guard_record_too = s->guard.enabled && s->guard_stepped && s->h_guard;
-  // (the guard's record -- t_contact, result, blocked: one contiguous piece -- rides along: rcsh_env_guard_last then needs no second wait)
-  if (guard_record_too) HIP_TRY(hipMemcpyAsync(s->h_guard, s->d_guard, align8(8 * (size_t)s->n) + align8(4 * (size_t)s->n) + (size_t)s->n, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  s->guard_host_valid = guard_record_too;
-  if (obs) std::memcpy(obs, s->h_pin + L.obs, sizeof(double) * s->n * ow);
-  if (info) std::memcpy(info, s->h_pin + L.info, (size_t)s->n * 8);
-  if (gw) std::memcpy(gw, s->h_pin + L.gw, sizeof(double) * s->n);
-  if (substeps) std::memcpy(substeps, s->h_pin + L.sub, sizeof(int32_t) * s->n);
-  return RCSH_OK;
+  return env_step_host(s, action, gripper, EnvOut{obs, info, gw, substeps, nullptr}, false);
 }
 
 // ---- depth renderer
@@ -2252,7 +2310,6 @@ int rcsh_sim_set_render_scene(rcsh_sim* s, const rcsh_render_scene_desc* d) {
       }
     }
   }
-  HIP_TRY(hipSetDevice(s->device));
   const bool first_scene = s->d_frames == nullptr;
   hipFree(s->d_rshapes); hipFree(s->d_rplanes); hipFree(s->d_frames); hipFree(s->d_wframes); hipFree(s->d_rcolours);
   hipFree(s->d_redge_planes); hipFree(s->d_redge_verts); hipFree(s->d_rviews);
@@ -2339,7 +2396,6 @@ int rcsh_sim_set_render_colours(rcsh_sim* s, const rcsh_render_colours* c) {
     col[i].square = w[6]; col[i].checker = w[7];
     if (col[i].checker != 0.0 && !(col[i].square > 0)) return fail(RCSH_ERR_ARG, "render colours: checker squares need a positive edge length");
   }
-  HIP_TRY(hipSetDevice(s->device));
   if (!s->d_rcolours) HIP_TRY(hipMalloc(&s->d_rcolours, sizeof(RenderColour) * ns));
   HIP_TRY(hipMemcpyAsync(s->d_rcolours, col.data(), sizeof(RenderColour) * ns, hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -2364,7 +2420,6 @@ int rcsh_sim_set_render_schedule(rcsh_sim* s, const int32_t* cam_ids, const doub
     if (cam_ids[c] < 0 || cam_ids[c] >= (int)s->cams.size()) return fail(RCSH_ERR_ARG, "render schedule: unknown camera id");
     if (!(seconds_between_calls[c] > 0)) return fail(RCSH_ERR_ARG, "render schedule: the period must be positive");
   }
-  HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipStreamSynchronize(s->stream));
   const size_t n = (size_t)s->n, nf = (size_t)s->nl + 9;
   // The same cameras with the same periods and a larger capacity: the schedule GROWS -- the cameras' clocks and what the last
@@ -2408,7 +2463,6 @@ int rcsh_render_pending(rcsh_sim* s, int32_t* count) {
   REQUIRE_SIM(s);
   if (!count) return fail(RCSH_ERR_ARG, "null output");
   if (s->rend.ncam == 0) return fail(RCSH_ERR_STATE, "no render schedule: call rcsh_sim_set_render_schedule first");
-  HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipMemcpyAsync(count, s->rend.count, sizeof(int32_t) * s->n, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   // more frames due in one launch than the schedule holds: the records beyond its capacity were not written (the newest are
@@ -2443,7 +2497,6 @@ int rcsh_camera_render_snapshot(rcsh_sim* s, int32_t cam_id, int32_t slot, uint8
   int which = -1;
   for (int c = 0; c < s->rend.ncam; ++c) which = s->rend_cam_id[c] == cam_id ? c : which;
   if (which < 0) return fail(RCSH_ERR_ARG, "camera is not part of the render schedule");
-  HIP_TRY(hipSetDevice(s->device));
   const size_t n = (size_t)s->n, nf = (size_t)s->nl + 9;
   // the frames kernel reads "the qpos the last position stage saw" and the box's pre-step pose through field offsets: point
   // it at the record instead of the state
@@ -2469,7 +2522,6 @@ int rcsh_camera_render_rgb_dev(rcsh_sim* s, int32_t cam_id, uint8_t* rgb, float*
   if (!s->d_frames) return fail(RCSH_ERR_STATE, "no render scene: call rcsh_sim_set_render_scene first");
   if (rgb && !s->rscene.colours) return fail(RCSH_ERR_STATE, "no colours: call rcsh_sim_set_render_colours first");
   if (cam_id < 0 || cam_id >= (int)s->cams.size()) return fail(RCSH_ERR_ARG, "unknown camera id");
-  HIP_TRY(hipSetDevice(s->device));
   const RenderCam& cam = s->cams[cam_id];
   hipError_t err = hipSuccess;
   bool ok = dispatch_topology(s->narm, s->grip, [&](auto topo) {
@@ -2517,18 +2569,12 @@ int rcsh_camera_render_dev(rcsh_sim* s, int32_t cam_id, float* depth_gl, uint16_
 int rcsh_camera_render_rgb(rcsh_sim* s, int32_t cam_id, uint8_t* rgb, float* depth_gl, uint16_t* depth_mm, double* cam_pose) {
   REQUIRE_SIM(s);
   if (cam_id < 0 || cam_id >= (int)s->cams.size()) return fail(RCSH_ERR_ARG, "unknown camera id");
-  HIP_TRY(hipSetDevice(s->device));
   const size_t px = (size_t)s->n * s->cams[cam_id].width * s->cams[cam_id].height;
   // device staging: f32 depth, u16 depth, camera poses (8-byte aligned), rgb
   const size_t off_mm = px * sizeof(float), off_pose = ((off_mm + px * sizeof(uint16_t) + 7) / 8) * 8, off_rgb = off_pose + sizeof(double) * 12 * s->n;
   const size_t need = off_rgb + 3 * px;
-  if (need > s->image_cap) {
-    hipFree(s->d_image);
-    s->d_image = nullptr; s->image_cap = 0;
-    HIP_TRY(hipMalloc(&s->d_image, need));
-    s->image_cap = need;
-  }
-  char* base = static_cast<char*>(s->d_image);
+  if (int rc = grow_device(s, s->d_image, need)) return rc;
+  char* base = static_cast<char*>(s->d_image.p);
   float* dgl = reinterpret_cast<float*>(base);
   uint16_t* dmm = reinterpret_cast<uint16_t*>(base + off_mm);
   double* dpose = reinterpret_cast<double*>(base + off_pose);
@@ -2955,7 +3001,7 @@ int rcsh_comm_allgather_dev(rcsh_sim* s, int32_t slot, const void* send_dev, voi
 
 int rcsh_env_allgather_obs_dev(rcsh_sim* s, int32_t slot, const double* local_obs_dev, double* all_obs_dev) {
   REQUIRE_SIM(s);
-  return rcsh_comm_allgather_dev(s, slot, local_obs_dev, all_obs_dev, sizeof(double) * (size_t)s->n * (14 + s->narm));
+  return rcsh_comm_allgather_dev(s, slot, local_obs_dev, all_obs_dev, sizeof(double) * (size_t)s->n * (kObsBase + s->narm));
 }
 
 int rcsh_comm_wait(rcsh_sim* s, int32_t slot, int32_t block_host) {
@@ -2993,13 +3039,11 @@ int rcsh_comm_destroy(rcsh_sim* s) {
 
 int rcsh_dev_alloc(rcsh_sim* s, size_t bytes, void** ptr) {
   REQUIRE_SIM(s);
-  HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipMalloc(ptr, bytes));
   return RCSH_OK;
 }
 int rcsh_dev_free(rcsh_sim* s, void* ptr) {
   REQUIRE_SIM(s);
-  HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipFree(ptr));
   return RCSH_OK;
 }
@@ -3097,7 +3141,6 @@ int rcsh_debug_dump_model(rcsh_sim* s, void* buf, size_t cap, size_t* size) {
 
 int rcsh_prof_enable(rcsh_sim* s, int32_t enable) {
   REQUIRE_SIM(s);
-  HIP_TRY(hipSetDevice(s->device));
   if (enable && s->ev_start.empty()) {
     s->ev_start.resize(kProfRing);
     s->ev_stop.resize(kProfRing);
