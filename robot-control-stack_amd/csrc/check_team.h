@@ -1,15 +1,15 @@
-// check_team.h -- "is this environment in a contact nobody resolves?", asked once per stepping launch.
+// check_team.h -- "can this environment have been in a contact nobody resolved?", asked once per stepping launch.
 //
 // The reference runs MuJoCo's collision pass in every substep (mj_step1, reference src/sim/sim.cpp:110) and whatever it finds
 // is resolved by mj_step2 (sim.cpp:112) -- in EVERY mode, also in Sim::step(k), where no collision callback looks at the
 // contact list (sim.cpp:108-115; the flags come from SimRobot::collision_callback, src/sim/SimRobot.cpp:172-182, which only
-// step_until_convergence invokes).  The kernels resolve the contacts they are compiled for: none in the lean instantiations
-// (the headline), robot <-> floor / cube in the CON ones, never robot <-> robot.  An environment whose geoms touch outside
-// that set steps on as if nothing had happened -- the arm passes through the floor or itself -- and from that substep on its
-// trajectory is not MuJoCo's.  This check makes that a reported fact instead of a premise: after the last substep of every
-// stepping launch the position the NEXT mj_step1 would collide is tested exactly (same predicates as the flag-only detection
-// of the convergence launches: sample points against the plane, MPR on every geom pair that survives two bounding tests), and
-// a hit sets the environment's sticky kContactUnresolved flag (info byte 7, cleared by Sim::reset).
+// step_until_convergence invokes).  The lean instantiations (the headline) resolve no contact; the contact-resolving ones resolve
+// robot <-> floor / cube and, without a free body, robot <-> robot.  This check lets a launch run lean: at its end it CERTIFIES that no
+// substep of the launch can have met a contact -- not only that the final position is free.  Per joint the substep loop keeps where the
+// joint has been; the levers (CheckTable::lev, host: model.cpp build_self_levers) turn that travel into a margin per geom pair and per
+// link above the floor; a pair is certified if its gap at the end (or at both ends, or the gap proven before: CheckTable::slack) exceeds it.
+// Gaps are lower bounds (spheres, oriented boxes, the support of A - B).  An environment that is not certified is marked: the contact-resolving
+// launch redoes its step from the lean launch's copy; where contacts are only flagged, a hit sets the sticky kContactUnresolved (info byte 7).
 //
 // Cost control, for a launch whose 17 substeps take ~240k cycles:
 //  * it runs once per launch, after the state has been written back: the team's LDS block is free then and serves as its

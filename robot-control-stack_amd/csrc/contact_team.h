@@ -657,12 +657,12 @@ RCSH_CONTACT_FN int dev_mpr(const Shape& A, const Shape& B, double* depth, doubl
 // Fall: world frames of the links of the wavefront's four teams, [4][NL][12] in LDS (R row-major, p); geoms welded to the
 // world carry their world frame in the table.  stage: LDS room for kSelfStage doubles.
 // Returns the class bits of the overlapping pairs of the calling lane's team.
-constexpr int kSelfStageVerts = 304;  // both hulls of a pair (host: build_self_pairs checks)
+constexpr int kSelfStageVerts = 304;  // both hulls of a pair (host: model.cpp list_geom_pairs checks)
 constexpr int kSelfStage = 3 * kSelfStageVerts;
 constexpr int kSelfSlots = 4;          // remembered separating directions per team (pair index, direction): a folded arm keeps three or four pairs near
 constexpr int kSelfCache = 4 * 4 * kSelfSlots;
 constexpr int kSelfTag = 2;            // which pair the stage holds
-constexpr int kMaxSelfPairs = 144;     // pairs whose bounding spheres the lean DET kernels keep in LDS (host: build_self_pairs)
+constexpr int kMaxSelfPairs = 144;     // pairs whose bounding spheres the lean DET kernels keep in LDS (host: model.cpp list_geom_pairs)
 constexpr int kSelfSphereWords = 10;   // per pair: c0, c1, r0 + r1 (inflated by the rounding) as float, the two links, the joints between them
 RCSH_D void self_geom_world(const ContactGeom& g, const double* F, double* R, double* p) {
   if (g.link < 0) {
@@ -1790,7 +1790,7 @@ RCSH_CONTACT_FN uint32_t contact_collide(const ContactTable& tab_, const CheckTa
           if (run && nc > 0) {
             const ContactGeom& ga = tab.geoms[g0];
             const ContactGeom& gb = tab.geoms[g1];
-            int c2 = 0;  // what the collision callbacks make of the pair (rcs_hip.hip: list_geom_pairs)
+            int c2 = 0;  // what the collision callbacks make of the pair (model.cpp: list_geom_pairs)
             if ((ga.cls | gb.cls) & 1) c2 |= 1;
             if (!((ga.cls & 4) && (gb.cls & 4)) && ((ga.cls | gb.cls) & 16) && !(gb.cls & 8)) c2 |= 2;
             const int la = ga.link >= 0 ? ga.link : kWorld, lb = gb.link >= 0 ? gb.link : kWorld;
@@ -1853,7 +1853,7 @@ RCSH_CONTACT_FN uint32_t contact_collide(const ContactTable& tab_, const CheckTa
         }
         nc = __builtin_amdgcn_readfirstlane(nc);
         if (nc > 0 && lane == 0) {
-          int c2 = 0;  // what the collision callbacks make of the pair (rcs_hip.hip: list_geom_pairs)
+          int c2 = 0;  // what the collision callbacks make of the pair (model.cpp: list_geom_pairs)
           if ((ga.cls | gb.cls) & 1) c2 |= 1;
           if (!((ga.cls & 4) && (gb.cls & 4)) && ((ga.cls | gb.cls) & 16) && !(gb.cls & 8)) c2 |= 2;
           const int la = ga.link >= 0 ? ga.link : kWorld, lb = gb.link >= 0 ? gb.link : kWorld;
@@ -1968,7 +1968,7 @@ RCSH_CONTACT_FN uint32_t contact_collide(const ContactTable& tab_, const CheckTa
           rem[0] = jk == 0 ? gf : rem[0]; rem[1] = jk == 1 ? gf : rem[1]; rem[2] = jk == 2 ? gf : rem[2];
         }
         if (nck > 0 && lane == 16 * k && nreg + nS < kMaxCon) {
-          int c2 = 0;  // what the collision callbacks make of the pair (rcs_hip.hip: list_geom_pairs)
+          int c2 = 0;  // what the collision callbacks make of the pair (model.cpp: list_geom_pairs)
           if ((ga.cls | gb.cls) & 1) c2 |= 1;
           if (!((ga.cls & 4) && (gb.cls & 4)) && ((ga.cls | gb.cls) & 16) && !(gb.cls & 8)) c2 |= 2;
           const int la = ga.link >= 0 ? ga.link : kWorld, lb = gb.link >= 0 ? gb.link : kWorld;

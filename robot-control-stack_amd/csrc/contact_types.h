@@ -2,6 +2,8 @@
 #pragma once
 #include <cstdint>
 
+#include "model.h"
+
 namespace rcsh {
 
 constexpr int kHullMaxVerts = 152;  // a collision hull the contact table admits has at most this many vertices (model.cpp: build_contact_table)
@@ -68,7 +70,7 @@ constexpr int kLevGeom = 144;  // CheckTable::lev: where the per-geom levers beg
 struct CheckTable {
   const CheckEntry* ent;
   const CheckGeom* geoms;
-  const float* lev; // [12][12] lev[j][l]: how far one radian (hinge) / metre (slide) of joint j moves a point of a geom ON link l (host: build_self_levers);
+  const float* lev; // [12][12] lev[j][l]: how far one radian (hinge) / metre (slide) of joint j moves a point of a geom ON link l (host: model.cpp build_self_levers);
                     // behind it (kLevGeom) [12][32]: the same for the points of geom g alone
   float* slack;    // [n][kSlackStride] self-contact stage of the contact phase (contact_team.h: contact_collide); null: every pair, every substep
   int32_t npair, ngeom;
@@ -82,6 +84,17 @@ struct CheckTable {
   int8_t pad3[4];
 };
 
+// Contact detection against the scene's static plane (flags only): sample points of the collision geoms, link frame
+struct CollTable {
+  const double* xyzr;      // [npts][4]
+  const uint8_t* cls;      // [npts] bit 0: geom is one of SimRobot's arm collision geoms; bit 1: SimGripper's
+  int32_t link_adr[kMaxLinks + 1];
+  double link_sphere[kMaxLinks][4];  // broad phase: bounding sphere of the link's points (link frame)
+  double link_aabb[kMaxLinks][6];    // broad phase of the contact phase: bounding box of the link's points (centre, half extents)
+  int32_t has_plane, has_static;     // has_static: link_aabb[NL] bounds collision geoms welded to the world (world frame)
+  double plane_n[3], plane_d;
+};
+
 struct ContactTable {
   const ContactGeom* geoms;
   const double* verts;   // [nvert][3] hull vertices, geom frame
@@ -90,7 +103,7 @@ struct ContactTable {
   int32_t link_geom_adr[13];  // geoms of link i are [link_geom_adr[i], link_geom_adr[i + 1]) (kMaxLinks + 1 entries)
   int32_t npair;
   // self collision: lever[j] bounds how far one radian (hinge) / one metre (slide) of joint j can move any point of a collision
-  // geom downstream of it (host: build_self_pairs) -- what turns joint motion into a bound on how much a pair's gap can close
+  // geom downstream of it (host: model.cpp build_self_levers) -- what turns joint motion into a bound on how much a pair's gap can close
   double self_lever[12];
   double plane_n[3], plane_d, plane_mu;
 };

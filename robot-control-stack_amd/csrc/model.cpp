@@ -7,6 +7,7 @@
 // rigid bodies) and the device loops shrink from 14 bodies to 9 links.
 #include "model_host.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -594,6 +595,308 @@ std::string build_contact_table(const HostModel& h, const DevModel& m, int plane
     geoms.push_back(cg);
   }
   return "";
+}
+
+// ---- collision tables (model_host.h: CollisionTables)
+
+GeomBox geom_box(const ContactGeom& g) {
+  GeomBox b;
+  double lc[3] = {0, 0, 0};  // the box's centre in the geom's frame
+  if (g.type == 7) for (int k = 0; k < 3; ++k) { lc[k] = g.aabb_c[k]; b.h[k] = g.aabb_h[k]; }
+  else if (g.type == 6) for (int k = 0; k < 3; ++k) b.h[k] = g.size[k];
+  else { b.h[0] = b.h[1] = g.size[0]; b.h[2] = g.size[0] + g.size[1]; }  // capsule (build_contact_table admits capsules, boxes and hulls only)
+  for (int k = 0; k < 3; ++k) b.c[k] = g.rot[3 * k] * lc[0] + g.rot[3 * k + 1] * lc[1] + g.rot[3 * k + 2] * lc[2] + g.pos[k];
+  for (int k = 0; k < 9; ++k) b.rot[k] = g.rot[k];
+  return b;
+}
+
+namespace {
+
+double norm3(const double* v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
+bool meshless_hull(const ContactGeom& g) { return g.type == 7 && g.vert_num == 0; }  // mesh blob missing from the checkout
+
+// joints on the path from the root to `link`, as a bit mask (arm link i: joints 0..i; a finger: the whole arm and its own slide;
+// welded to the world: none)
+int root_joints(int link, int narm) {
+  if (link < 0) return 0;
+  if (link < narm) return (1 << (link + 1)) - 1;
+  return ((1 << narm) - 1) | (1 << link);
+}
+// the deepest link both links descend from or are; -1: none, the world
+int common_ancestor_link(int l0, int l1, int narm) {
+  for (int k = l0; k >= 0; k = parent_link(k, narm))
+    for (int a = l1; a >= 0; a = parent_link(a, narm))
+      if (a == k) return k;
+  return -1;
+}
+
+}  // namespace
+
+// A geom welded to the world against a geom of the arm's first link (MuJoCo's parent-child filter lets the pair through: the parent is
+// static): ONE hinge moves them relative to each other, and a rotation leaves every point's coordinate ALONG the hinge's axis alone.  If
+// the two geoms' extents along that axis do not overlap, no joint angle brings them into contact -- the pair is dropped from the tables
+// (the FR3's link 1 sits on link 0 with 0.1 mm between the hulls: the pair survived every bounding test in every pose, and the contact
+// phase refined it in every substep of every escalated environment).
+bool never_touch_across_first_hinge(const DevModel& m, const std::vector<double>& cverts, const ContactGeom& a, const ContactGeom& b) {
+  const ContactGeom* w = a.link < 0 ? &a : (b.link < 0 ? &b : nullptr);
+  const ContactGeom* l = a.link == 0 ? &a : (b.link == 0 ? &b : nullptr);
+  if (!w || !l || m.jtype[0] == kSlide) return false;
+  double ax[3] = {m.axis[0][0], m.axis[0][1], m.axis[0][2]}, aw[3];
+  for (int k = 0; k < 3; ++k) aw[k] = m.rot0[0][3 * k] * ax[0] + m.rot0[0][3 * k + 1] * ax[1] + m.rot0[0][3 * k + 2] * ax[2];
+  // (NOT geom_box: the geom's own extent along one direction -- a hull's over its vertices, a capsule's as a capsule -- which is tighter
+  // than its box's, and the 0.1 mm above need it)
+  auto extent = [&](const ContactGeom& g, const double* u, double& lo, double& hi) {
+    // of the geom along u, both in the frame of the geom's link
+    double ug[3];  // u in the geom's frame
+    for (int k = 0; k < 3; ++k) ug[k] = g.rot[k] * u[0] + g.rot[3 + k] * u[1] + g.rot[6 + k] * u[2];
+    const double c = u[0] * g.pos[0] + u[1] * g.pos[1] + u[2] * g.pos[2];
+    if (g.type == 7) {
+      lo = 1e300; hi = -1e300;
+      for (int v = 0; v < g.vert_num; ++v) {
+        const double* x = &cverts[3 * (size_t)(g.vert_adr + v)];
+        const double d = c + ug[0] * x[0] + ug[1] * x[1] + ug[2] * x[2];
+        lo = std::min(lo, d); hi = std::max(hi, d);
+      }
+    } else {
+      double e;
+      if (g.type == 6) e = std::fabs(ug[0]) * g.size[0] + std::fabs(ug[1]) * g.size[1] + std::fabs(ug[2]) * g.size[2];
+      else if (g.type == 3) e = std::fabs(ug[2]) * g.size[1] + g.size[0];
+      else e = g.size[0];
+      lo = c - e; hi = c + e;
+    }
+  };
+  double wlo, whi, llo, lhi;
+  extent(*w, aw, wlo, whi);
+  extent(*l, ax, llo, lhi);
+  const double off = aw[0] * m.pos0[0][0] + aw[1] * m.pos0[0][1] + aw[2] * m.pos0[0][2];
+  llo += off; lhi += off;
+  if (meshless_hull(*w) || meshless_hull(*l)) return false;
+  return llo - whi > 1e-7 || wlo - lhi > 1e-7;
+}
+
+namespace {
+
+// MuJoCo's pair filters on two collision geoms of the robot (mj_collision: different weld bodies -- here: links; no
+// parent-child pair unless one of the two is welded to the world), then what the callbacks make of a contact of the pair
+// (SimRobot.cpp:172-182: either geom is an arm collision geom; SimGripper.cpp:108-130: not finger-finger, either geom is a
+// gripper collision geom, geom[1] is not in the ignore list -- quirk Q6).
+// All pairs the filters admit; `reacting_only`: drop those no collision callback reacts to (cls == 0).
+std::vector<SelfPair> list_geom_pairs(const HostModel& h, const DevModel& m, const std::vector<ContactGeom>& cgeoms, const std::vector<double>& cverts,
+                                      bool reacting_only) {
+  std::vector<SelfPair> out;
+  const int ng = (int)cgeoms.size(), narm = m.narm;
+  for (int i = 0; i < ng; ++i)
+    for (int j = i + 1; j < ng; ++j) {
+      const ContactGeom &a = cgeoms[i], &b = cgeoms[j];
+      if (a.link == b.link) continue;
+      if (a.link >= 0 && b.link >= 0 && (parent_link(a.link, narm) == b.link || parent_link(b.link, narm) == a.link)) continue;
+      // MuJoCo's mask filter: the pair collides if (contype0 & conaffinity1) || (contype1 & conaffinity0) (pairs the masks exclude
+      // would raise the sticky flags -- and send an environment to the contact-resolving launch)
+      const auto &ct = h.geom_contype, &ca = h.geom_conaffinity;
+      if (a.geom_id < (int)ct.size() && b.geom_id < (int)ct.size() && a.geom_id < (int)ca.size() && b.geom_id < (int)ca.size() &&
+          !((ct[a.geom_id] & ca[b.geom_id]) || (ct[b.geom_id] & ca[a.geom_id])))
+        continue;
+      if (meshless_hull(a) || meshless_hull(b)) continue;
+      if (a.vert_num + b.vert_num > kSelfStageVertsHost) continue;  // (the contact table admits hulls of at most 152 vertices each: build_contact_table)
+      if (never_touch_across_first_hinge(m, cverts, a, b)) continue;
+      const bool swap = a.type > b.type;  // geom[0] / geom[1] of the contact: by type, then by id (the table is in id order)
+      const ContactGeom &g0 = swap ? b : a, &g1 = swap ? a : b;
+      int cls = 0;
+      if ((g0.cls | g1.cls) & 1) cls |= 1;
+      if (!((g0.cls & 4) && (g1.cls & 4)) && ((g0.cls | g1.cls) & 16) && !(g1.cls & 8)) cls |= 2;
+      if (!cls && reacting_only) continue;
+      SelfPair pr{};
+      pr.g0 = (int16_t)(swap ? j : i); pr.g1 = (int16_t)(swap ? i : j);
+      pr.l0 = (int16_t)g0.link; pr.l1 = (int16_t)g1.link;
+      pr.cls = cls;
+      // joints on the tree path between the two links: the root paths' symmetric difference
+      pr.joints = root_joints(g0.link, narm) ^ root_joints(g1.link, narm);
+      auto bounds = [](const ContactGeom& g, double* c, double& r, double* rot, double* hh) {
+        const GeomBox bx = geom_box(g);
+        std::memcpy(c, bx.c, sizeof(bx.c)); std::memcpy(hh, bx.h, sizeof(bx.h)); std::memcpy(rot, bx.rot, sizeof(bx.rot));
+        r = norm3(bx.h);  // the bounding sphere: the box's half diagonal
+      };
+      bounds(g0, pr.c0, pr.r0, pr.rot0, pr.h0);
+      bounds(g1, pr.c1, pr.r1, pr.rot1, pr.h1);
+      out.push_back(pr);
+    }
+  return out;
+}
+
+// The tables of the end-of-launch check for contacts nobody resolves (check_team.h): ALL admitted geom pairs (full records for the
+// box test and the narrow phase, packed entries for the sphere test).  Pairs of the same two bodies stay together, so that a
+// cluster of pairs that come near at once (the two fingers' pads when the gripper closes) spreads over the lanes.
+void build_check_table(const HostModel& h, const DevModel& m, const std::vector<ContactGeom>& cgeoms, const std::vector<double>& cverts, CollisionTables& t) {
+  t.chk_pairs = list_geom_pairs(h, m, cgeoms, cverts, false);
+  auto key = [](const SelfPair& p) { const int a = std::min(p.l0, p.l1) + 1, b = std::max(p.l0, p.l1) + 1; return a * 64 + b; };
+  std::stable_sort(t.chk_pairs.begin(), t.chk_pairs.end(), [&](const SelfPair& x, const SelfPair& y) { return key(x) < key(y); });
+  // (a scene with more admitted pairs than a lane keeps entries for is NOT refused -- plain Sim.step users never read the flag --: the
+  // pairs past the capacity stay unchecked, counted and reported: rcsh_sim_contact_check_unchecked_pairs)
+  t.chk_unchecked = 0;
+  if ((int)t.chk_pairs.size() > kMaxCheckPairs) {
+    t.chk_unchecked = (int)t.chk_pairs.size() - kMaxCheckPairs;
+    t.chk_pairs.resize(kMaxCheckPairs);
+  }
+  t.chk_ent.clear();
+  for (const auto& p : t.chk_pairs) {
+    CheckEntry e{};
+    // (bits 16-23: 1 + the deepest link both geoms' links descend from or are -- 0: none, the world; the slack test charges each geom
+    // with the joints below it)
+    e.geoms = (uint32_t)p.g0 | ((uint32_t)p.g1 << 8) | ((uint32_t)(common_ancestor_link(p.l0, p.l1, m.narm) + 1) << 16);
+    e.rsum = (float)(p.r0 + p.r1) * 1.000001f + 2e-6f;  // (single-precision centres: the sum of the radii rounded up)
+    t.chk_ent.push_back(e);
+  }
+  // the geoms' bounding boxes in their links' frames (what SelfPair carries per pair, once per geom)
+  t.chk_geoms.clear();
+  for (const auto& cg : cgeoms) {
+    const GeomBox bx = geom_box(cg);
+    CheckGeom g{};
+    std::memcpy(g.c, bx.c, sizeof(g.c)); std::memcpy(g.rot, bx.rot, sizeof(g.rot));
+    t.chk_geoms.push_back(g);
+  }
+}
+
+// self_lever[j]: how far one radian of hinge j (one metre of a slide) can move a point of any collision geom downstream of it.
+// Distances between consecutive joint anchors are constants of the links; a finger's anchor slides, so its stroke is added.
+void build_self_levers(const DevModel& m, const std::vector<ContactGeom>& cgeoms, double* self_lever, float* link_lever) {
+  const int na = m.narm, nl = m.nl;
+  // per geom on a link: its box relative to the link's joint anchor (centre c, link frame), and the farthest the anchor is from a point of it
+  struct Anchored { GeomBox box; double dist; };
+  std::vector<Anchored> ab(cgeoms.size());
+  // reach[L]: from link L's joint anchor to the farthest point of a collision geom ON link L (link frame)
+  std::vector<double> reach(nl, 0.0), hop(nl, 0.0), stroke(nl, 0.0);
+  for (size_t gi = 0; gi < cgeoms.size(); ++gi) {
+    const auto& g = cgeoms[gi];
+    if (g.link < 0) continue;
+    Anchored& a = ab[gi];
+    a.box = geom_box(g);
+    for (int k = 0; k < 3; ++k) a.box.c[k] -= m.jpos[g.link][k];
+    a.dist = norm3(a.box.c) + norm3(a.box.h);
+    reach[g.link] = std::max(reach[g.link], a.dist);
+  }
+  for (int L = 0; L < nl; ++L) {
+    // hop[L]: from the parent link's anchor to link L's anchor (parent link frame, at qpos0; a hinge's anchor does not move)
+    const int p = parent_link(L, na);
+    double a[3];
+    for (int k = 0; k < 3; ++k) a[k] = m.pos0[L][k] + m.rot0[L][3 * k] * m.jpos[L][0] + m.rot0[L][3 * k + 1] * m.jpos[L][1] + m.rot0[L][3 * k + 2] * m.jpos[L][2] - (p >= 0 ? m.jpos[p][k] : 0.0);
+    hop[L] = norm3(a);
+    if (m.jtype[L] == kSlide) stroke[L] = std::max(std::fabs(m.range[L][0] - m.qpos0[L]), std::fabs(m.range[L][1] - m.qpos0[L]));
+  }
+  // far[L]: from link L's anchor to the farthest geom point on L or downstream of it
+  std::vector<double> far(nl, 0.0);
+  for (int L = nl - 1; L >= 0; --L) {
+    far[L] = std::max(far[L], reach[L] + stroke[L]);
+    const int p = parent_link(L, na);
+    if (p >= 0) far[p] = std::max(far[p], hop[L] + stroke[L] + far[L]);
+  }
+  for (int j = 0; j < 12; ++j) self_lever[j] = 0.0;
+  for (int j = 0; j < nl; ++j) self_lever[j] = m.jtype[j] == kSlide ? 1.0 : 1.01 * far[j] + kLeverSlack;
+  // link_lever[j][l]: the same bound for the geoms ON link l alone (j an ancestor-or-self joint of l) -- what the contact phase's slack
+  // test charges a geom pair / a geom above the floor with.  The isotropic lever above takes the whole arm's reach for joint 1; the pair
+  // (link 0, link 2), whose hulls stay a centimetre apart in every pose, sits 0.2 m from that axis: charged with 1.2 m per radian it was
+  // due in nearly every substep, and with it the whole collision pass.
+  for (int k = 0; k < kLevGeom + 12 * 32; ++k) link_lever[k] = 0.0f;
+  for (int l = 0; l < nl; ++l) {
+    double acc = reach[l];  // from link l's anchor to the farthest point of a geom on l
+    for (int j = l; j >= 0; j = parent_link(j, na)) {
+      // acc: from joint j's anchor to the farthest point of a geom on l, over every configuration of the joints in between
+      link_lever[j * 12 + l] = (float)(m.jtype[j] == kSlide ? 1.0 : (1.01 * (acc + stroke[l]) + kLeverSlack) * 1.000001);
+      acc += hop[j] + stroke[j];
+    }
+  }
+  // ... and per GEOM (kLevGeom + j * 32 + g): the same bound for the points of geom g alone.  A link's lever is its farthest geom's: link 7
+  // carries the flange's hull AND the hand's, 0.2 m from its joint, and the pair (link 5's hull, the flange's hull) -- 14-17 mm apart in
+  // every pose -- was charged the hand's reach: in step_until_convergence, whose launches move a joint by up to five degrees, its
+  // certificate failed in a third of the batch at every step (check_team.h: the narrow phase's second chance).
+  static_assert(kMaxCGeom <= 32, "a column per collision geom");
+  for (size_t gi = 0; gi < cgeoms.size() && gi < 32; ++gi) {
+    const int l = cgeoms[gi].link;
+    if (l < 0) continue;
+    const GeomBox& bx = ab[gi].box;
+    double acc = ab[gi].dist;
+    // (the geom's OWN hinge: what a radian of it moves is a point's distance from the AXIS, not from the anchor -- the largest over the
+    // eight corners of the geom's box; a flange that is a cylinder about its joint's axis: its radius instead of its length)
+    double radial = 0.0;
+    for (int corner = 0; corner < 8; ++corner) {
+      const double sg[3] = {corner & 1 ? bx.h[0] : -bx.h[0], corner & 2 ? bx.h[1] : -bx.h[1], corner & 4 ? bx.h[2] : -bx.h[2]};
+      double v[3];
+      for (int k = 0; k < 3; ++k) v[k] = bx.c[k] + bx.rot[3 * k] * sg[0] + bx.rot[3 * k + 1] * sg[1] + bx.rot[3 * k + 2] * sg[2];
+      const double* ax = m.axis[l];
+      const double an = norm3(ax);
+      const double al = an > 0 ? (v[0] * ax[0] + v[1] * ax[1] + v[2] * ax[2]) / an : 0.0;
+      const double r2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2] - al * al;
+      radial = std::max(radial, std::sqrt(std::max(r2, 0.0)));
+    }
+    for (int j = l; j >= 0; j = parent_link(j, na)) {
+      const double arm = j == l && m.jtype[j] != kSlide ? std::min(radial, acc) : acc + stroke[l];
+      link_lever[kLevGeom + j * 32 + (int)gi] = (float)(m.jtype[j] == kSlide ? 1.0 : (1.01 * arm + kLeverSlack) * 1.000001);
+      acc += hop[j] + stroke[j];
+    }
+  }
+}
+
+}  // namespace
+
+void build_collision_tables(const HostModel& h, const DevModel& m, const CollisionPoints& cp, const std::vector<ContactGeom>& cgeoms,
+                            const std::vector<double>& cverts, CollisionTables& t) {
+  t = CollisionTables();
+  std::memset(&t.coll, 0, sizeof(t.coll));  // (padding included: the kernels get these bytes as arguments)
+  std::memset(&t.ctab, 0, sizeof(t.ctab));
+  std::memset(&t.chk, 0, sizeof(t.chk));
+  const int ng = (int)cgeoms.size();
+  // ---- Params::coll: the sample points' broad phase and the plane
+  for (int i = 0; i <= kMaxLinks; ++i) t.coll.link_adr[i] = i < (int)cp.link_adr.size() ? cp.link_adr[i] : (cp.link_adr.empty() ? 0 : cp.link_adr.back());
+  for (int i = 0; i < kMaxLinks; ++i)
+    for (int a = 0; a < 4; ++a) t.coll.link_sphere[i][a] = (size_t)(4 * i + a) < cp.link_sphere.size() ? cp.link_sphere[4 * i + a] : 0.0;
+  for (int i = 0; i < kMaxLinks; ++i)
+    for (int a = 0; a < 6; ++a) t.coll.link_aabb[i][a] = (size_t)(6 * i + a) < cp.link_aabb.size() ? cp.link_aabb[6 * i + a] : 0.0;
+  // entry nl: the box (world frame) around the robot's collision geoms that are welded to the world (link 0's hull): the
+  // broad phase of the contact phase tests the free body against it on the first lane that carries no link
+  double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+  bool any = false;
+  for (const auto& g : cgeoms) {
+    if (g.link >= 0 || meshless_hull(g)) continue;
+    const GeomBox bx = geom_box(g);
+    for (int a = 0; a < 3; ++a) {
+      const double e = std::fabs(bx.rot[3 * a]) * bx.h[0] + std::fabs(bx.rot[3 * a + 1]) * bx.h[1] + std::fabs(bx.rot[3 * a + 2]) * bx.h[2];
+      lo[a] = std::fmin(lo[a], bx.c[a] - e); hi[a] = std::fmax(hi[a], bx.c[a] + e);
+    }
+    any = true;
+  }
+  if (any && m.nl < kMaxLinks)
+    for (int a = 0; a < 3; ++a) { t.coll.link_aabb[m.nl][a] = 0.5 * (lo[a] + hi[a]); t.coll.link_aabb[m.nl][3 + a] = 0.5 * (hi[a] - lo[a]); }
+  t.coll.has_static = any ? 1 : 0;
+  t.coll.has_plane = cp.has_plane && !cp.geom.empty();
+  for (int k = 0; k < 3; ++k) t.coll.plane_n[k] = t.ctab.plane_n[k] = cp.plane_n[k];
+  t.coll.plane_d = t.ctab.plane_d = cp.plane_d;
+  // ---- Params::ctab and Params::chk: per geom
+  t.ctab.has_plane = cp.has_plane;
+  // geoms of a link are contiguous in the table (geom order = body order); geoms welded to the world sit in front
+  static_assert(kMaxLinks + 1 == 13, "ContactTable::link_geom_adr");
+  int idx = 0;
+  while (idx < ng && cgeoms[idx].link < 0) ++idx;
+  for (int i = 0; i < kMaxLinks; ++i) {
+    t.ctab.link_geom_adr[i] = idx;
+    while (idx < ng && cgeoms[idx].link == i) ++idx;
+  }
+  t.ctab.link_geom_adr[kMaxLinks] = idx;
+  t.chk.ngeom = ng;
+  t.chk.plane_points = t.coll.has_plane ? 1 : 0;
+  for (int g = 0; g < ng && g < kMaxCGeom; ++g) {
+    const ContactGeom& cg = cgeoms[g];
+    const GeomBox bx = geom_box(cg);
+    for (int k = 0; k < 3; ++k) t.chk.gh[g][k] = bx.h[k];
+    t.chk.gvert[g][0] = cg.vert_adr; t.chk.gvert[g][1] = cg.type == 7 ? cg.vert_num : 0;
+    t.chk.glink[g] = (int8_t)cg.link;
+    t.chk.gtype[g] = (int8_t)cg.type;
+  }
+  if (cgeoms.empty()) return;
+  // ---- the pair tables and the levers
+  t.pairs = list_geom_pairs(h, m, cgeoms, cverts, true);
+  build_self_levers(m, cgeoms, t.ctab.self_lever, t.link_lever);
+  build_check_table(h, m, cgeoms, cverts, t);
+  t.ctab.npair = (int)t.pairs.size();
+  t.chk.npair = (int)t.chk_ent.size();  // (also the pair table of the contact phase's self-contact stage)
 }
 
 bool build_hull_edges(const double* planes, int np, std::vector<HullEdge>& edges, double centre[3]) {

@@ -55,6 +55,46 @@ std::string build_contact_table(const HostModel& h, const DevModel& m, int plane
                                 std::string& overflow /* geoms left out of the table because of a capacity limit: why (empty: none) */,
                                 std::vector<int>* dropped = nullptr /* their mjModel geom ids */);
 
+// ---- collision tables: everything the kernels' collision tests read that is fixed between two changes of the geoms' class bits.
+// Pure functions of the model -- no device, no environment variable -- so that the bounds the certificate rests on can be tested on a CPU
+// (tests/test_collision_tables_cpu.py).
+
+// link i's parent: i - 1 along the arm; both fingers hang off the arm's last link; -1: the world
+inline int parent_link(int link, int narm) { return link < narm ? link - 1 : narm - 1; }
+
+// A collision geom's bounding box in the frame of its link (the world's, for a geom welded to it): centre, half extents along the
+// geom's axes, and those axes (the geom's frame in the link's, row-major).  Hull: the box of its vertices; box: its size; capsule:
+// (r, r, r + half length).  THE rule: the pair records, the check's per-geom tables, the levers and the static geoms' world box use it.
+struct GeomBox {
+  double c[3], h[3], rot[9];
+};
+GeomBox geom_box(const ContactGeom& g);
+
+constexpr int kSelfStageVertsHost = 304;  // contact_team.h: kSelfStageVerts (device code; rcs_hip.hip asserts that the two agree)
+// The additive slack of every hinge lever (metres per radian, on top of the 1 % factor).  A chain from a hinge to a geom holds at most
+// one slide, whose stroke the lever includes: so the levers also hold for a slide up to kLeverSlack PAST its stroke.  The collision
+// guard leans on that (rcs_hip.hip guard_launch: kGuardSlideTol).
+constexpr double kLeverSlack = 1e-3;
+
+struct CollisionTables {
+  std::vector<SelfPair> pairs;        // the admitted geom pairs a collision callback reacts to (cls != 0): the contact phase's self-collision pairs
+  std::vector<SelfPair> chk_pairs;    // ALL admitted geom pairs, by body pair, at most kMaxCheckPairs of them ...
+  std::vector<CheckEntry> chk_ent;    // ... and their packed entries (CheckTable::ent)
+  std::vector<CheckGeom> chk_geoms;   // the geoms' boxes in their links' frames (CheckTable::geoms)
+  int chk_unchecked = 0;              // admitted pairs past kMaxCheckPairs: neither checked at the end of a launch nor resolved as self contacts
+  float link_lever[kLevGeom + 12 * 32] = {0};  // CheckTable::lev: [joint][link], then per GEOM [joint][geom] (kLevGeom)
+  // The launch-invariant contents of Params::coll / ctab / chk (every byte defined, pointers null).  The launch fills in the device
+  // pointers, ctab.ngeom, ctab.plane_mu and chk.pad.  ctab.self_lever holds the per-joint levers (no second copy of them).
+  CollTable coll;
+  ContactTable ctab;
+  CheckTable chk;
+};
+// A scene without collision geoms gets the sample points' part of `coll` and the plane alone: no pairs, levers zero.
+void build_collision_tables(const HostModel& h, const DevModel& m, const CollisionPoints& cp, const std::vector<ContactGeom>& cgeoms,
+                            const std::vector<double>& cverts, CollisionTables& out);
+// the pieces, for the tests: is the pair (a geom welded to the world, a geom of the arm's first link) out of reach in every pose?
+bool never_touch_across_first_hinge(const DevModel& m, const std::vector<double>& cverts, const ContactGeom& a, const ContactGeom& b);
+
 // Edges of the convex polytope { x : n_i . x <= d_i } a drawn hull is given as (render.h: the ray caster finds a hull's outline
 // as seen from the camera among them).  Each edge: the two planes that meet in it and its end points.  `centre`: a point
 // inside (the mean of the polytope's vertices).  false: the planes do not bound a polytope this routine can vouch for

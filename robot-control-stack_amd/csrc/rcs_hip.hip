@@ -89,18 +89,12 @@ struct rcsh_sim {
   std::vector<int> cgeoms_dropped;  // mjModel ids of those geoms: invisible to geom-geom detection (the floor test by sample points still sees them)
   std::vector<double> cverts;
   ContactGeom* d_cgeoms = nullptr;
-  SelfPair* d_pairs = nullptr;       // self-collision pairs a collision callback reacts to (rebuilt when the class bits change)
-  std::vector<SelfPair> pairs;
-  double self_lever[12] = {0};       // contact_types.h: ContactTable::self_lever
   double* d_cverts = nullptr;
-  // the once-per-launch check for contacts nobody resolves (check_team.h): every geom pair MuJoCo's filters let collide, by body pair
-  std::vector<SelfPair> chk_pairs;
-  std::vector<CheckEntry> chk_ent;
-  std::vector<CheckGeom> chk_geoms;
-  CheckGeom* d_chk_geoms = nullptr;
-  CheckEntry* d_chk_ent = nullptr;
-  float link_lever[12 * 12 + 12 * 32] = {0};  // contact_types.h: CheckTable::lev ([joint][link]), then the same per GEOM ([joint][geom], kLevGeom)
-  float* d_lev = nullptr;
+  // what the collision tests may skip (model.cpp: build_collision_tables; rebuilt when the class bits change) and its device copies: the
+  // self-collision pairs a collision callback reacts to; the once-per-launch check for contacts nobody resolves (check_team.h)
+  CollisionTables tables;
+  Grown d_pairs, d_chk_ent, d_chk_geoms;  // SelfPair[], CheckEntry[], CheckGeom[]
+  float* d_lev = nullptr;            // tables.link_lever
   float* d_slack = nullptr;          // [n][kSlackStride]: the self-contact stage's remaining gaps per pair + the joints it saw last (CheckTable::slack)
   Grown d_query;                     // staging of the host-pointer collision queries (rcsh_collision_query / rcsh_motion_query) and of the peek's action
   // the environments' collision guard (guard_team.h; rcsh_env_configure_guard): its settings, and two records of [result | t_contact |
@@ -110,7 +104,6 @@ struct rcsh_sim {
   bool guard_stepped = false;        // a guarded step has filled the first record
   char* h_guard = nullptr;           // page-locked copy of that record: rcsh_env_step fetches it with its own outputs (one synchronisation)
   bool guard_host_valid = false;     // ... and it is the last guarded step's
-  int chk_unchecked = 0;             // admitted geom pairs past kMaxCheckPairs: neither checked at the end of a launch nor resolved as self contacts
   // per-environment escalation (sim_kernels.h: RunOp::esc_role): a step is the lean launch over the environments not in contact plus
   // the contact-resolving launch over the others
   bool esc_mode = false;
@@ -188,40 +181,14 @@ namespace {
 
 int grid_for(int n) { return (n + kBlock - 1) / kBlock; }
 
+// The launch-invariant blocks come prebuilt (CollisionTables); a launch adds the pointers and what its configuration decides.
 Params make_params(rcsh_sim* s) {
+  const CollisionTables& t = s->tables;
   Params P;
   P.model = s->d_model;
+  std::memcpy(&P.coll, &t.coll, sizeof(P.coll));
   P.coll.xyzr = s->d_coll_xyzr;
   P.coll.cls = s->d_coll_cls;
-  for (int i = 0; i <= kMaxLinks; ++i) P.coll.link_adr[i] = i < (int)s->cp.link_adr.size() ? s->cp.link_adr[i] : (s->cp.link_adr.empty() ? 0 : s->cp.link_adr.back());
-  for (int i = 0; i < kMaxLinks; ++i)
-    for (int a = 0; a < 4; ++a) P.coll.link_sphere[i][a] = (size_t)(4 * i + a) < s->cp.link_sphere.size() ? s->cp.link_sphere[4 * i + a] : 0.0;
-  for (int i = 0; i < kMaxLinks; ++i)
-    for (int a = 0; a < 6; ++a) P.coll.link_aabb[i][a] = (size_t)(6 * i + a) < s->cp.link_aabb.size() ? s->cp.link_aabb[6 * i + a] : 0.0;
-  {
-    // entry nl: the box (world frame) around the robot's collision geoms that are welded to the world (link 0's hull): the
-    // broad phase of the contact phase tests the free body against it on the first lane that carries no link
-    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    bool any = false;
-    for (const auto& g : s->cgeoms) {
-      if (g.link >= 0 || (g.type == 7 && g.vert_num == 0)) continue;
-      double lc[3] = {0, 0, 0}, h[3] = {g.size[0], g.size[1], g.size[2]};
-      if (g.type == 7) for (int k = 0; k < 3; ++k) { lc[k] = g.aabb_c[k]; h[k] = g.aabb_h[k]; }
-      else if (g.type == 3) { h[0] = h[1] = g.size[0]; h[2] = g.size[0] + g.size[1]; }
-      for (int a = 0; a < 3; ++a) {
-        const double c = g.rot[3 * a] * lc[0] + g.rot[3 * a + 1] * lc[1] + g.rot[3 * a + 2] * lc[2] + g.pos[a];
-        const double e = std::fabs(g.rot[3 * a]) * h[0] + std::fabs(g.rot[3 * a + 1]) * h[1] + std::fabs(g.rot[3 * a + 2]) * h[2];
-        lo[a] = std::fmin(lo[a], c - e); hi[a] = std::fmax(hi[a], c + e);
-      }
-      any = true;
-    }
-    if (any && s->nl < kMaxLinks)
-      for (int a = 0; a < 3; ++a) { P.coll.link_aabb[s->nl][a] = 0.5 * (lo[a] + hi[a]); P.coll.link_aabb[s->nl][3 + a] = 0.5 * (hi[a] - lo[a]); }
-    P.coll.has_static = any ? 1 : 0;
-  }
-  P.coll.has_plane = s->cp.has_plane && !s->cp.geom.empty();
-  for (int k = 0; k < 3; ++k) P.coll.plane_n[k] = s->cp.plane_n[k];
-  P.coll.plane_d = s->cp.plane_d;
   P.S = s->S;
   P.flags = s->flags;
   P.conv_steps = s->conv;
@@ -232,58 +199,22 @@ Params make_params(rcsh_sim* s) {
   P.grip = s->gripcfg;
   P.env = s->env;
   P.boxtask = s->d_boxtask;
+  P.rend = s->rend;
+  std::memcpy(&P.ctab, &t.ctab, sizeof(P.ctab));
   P.ctab.geoms = s->d_cgeoms;
   P.ctab.verts = s->d_cverts;
-  P.rend = s->rend;
-  P.ctab.pairs = s->d_pairs;
-  for (int k = 0; k < 12; ++k) P.ctab.self_lever[k] = s->self_lever[k];
-  P.ctab.npair = (int)s->pairs.size();
+  P.ctab.pairs = static_cast<const SelfPair*>(s->d_pairs.p);
   P.ctab.ngeom = s->box.resolve ? (int)s->cgeoms.size() : 0;
-  P.ctab.has_plane = s->cp.has_plane;
-  {
-    // geoms of a link are contiguous in the table (geom order = body order); geoms welded to the world sit in front
-    static_assert(kMaxLinks + 1 == 13, "ContactTable::link_geom_adr");
-    for (int i = 0; i <= kMaxLinks; ++i) P.ctab.link_geom_adr[i] = 0;
-    int idx = 0;
-    const int ng = (int)s->cgeoms.size();
-    while (idx < ng && s->cgeoms[idx].link < 0) ++idx;
-    for (int i = 0; i < kMaxLinks; ++i) {
-      P.ctab.link_geom_adr[i] = idx;
-      while (idx < ng && s->cgeoms[idx].link == i) ++idx;
-    }
-    P.ctab.link_geom_adr[kMaxLinks] = idx;
-  }
-  for (int k = 0; k < 3; ++k) P.ctab.plane_n[k] = s->cp.plane_n[k];
-  P.ctab.plane_d = s->cp.plane_d;
   P.ctab.plane_mu = s->plane_mu;
-  P.chk.ent = s->d_chk_ent;
+  std::memcpy(&P.chk, &t.chk, sizeof(P.chk));
+  P.chk.ent = static_cast<const CheckEntry*>(s->d_chk_ent.p);
   P.chk.lev = s->d_lev;
-  P.chk.geoms = s->d_chk_geoms;
+  P.chk.geoms = static_cast<const CheckGeom*>(s->d_chk_geoms.p);
   P.chk.slack = s->d_slack;
-  P.chk.npair = (int)s->chk_ent.size();  // (also the pair table of the contact phase's self-contact stage)
-  P.chk.ngeom = (int)s->cgeoms.size();
-  P.chk.plane_points = P.coll.has_plane ? 1 : 0;
-  P.chk.pad = 0;
   if (const char* dm = std::getenv("RCSH_CHECK_SKIP")) P.chk.pad = std::atoi(dm);  // development: bit 0 no narrow phase, 1 no boxes, 2 no spheres, 3 no
   // Gilbert fallback, 4 no slack record (timing experiments, check_team.h); bit 5 sends every coupled environment of a box-less scene to the
   // wide solve (contact_wide.h) whatever its contact count, not only those with more than kDenseCon contacts (contact_dense.h; the tests
   // of the wide solve's math on few contacts, tests/test_gpu_contact_wide.py).  Read on every launch.
-  std::memset(P.chk.gh, 0, sizeof(P.chk.gh));
-  std::memset(P.chk.gvert, 0, sizeof(P.chk.gvert));
-  std::memset(P.chk.glink, 0, sizeof(P.chk.glink));
-  std::memset(P.chk.pad2, 0, sizeof(P.chk.pad2));
-  std::memset(P.chk.gtype, 0, sizeof(P.chk.gtype));
-  std::memset(P.chk.pad3, 0, sizeof(P.chk.pad3));
-  for (size_t g = 0; g < s->cgeoms.size() && g < (size_t)kMaxCGeom; ++g) {
-    const ContactGeom& cg = s->cgeoms[g];
-    double* h = P.chk.gh[g];
-    if (cg.type == 7) for (int k = 0; k < 3; ++k) h[k] = cg.aabb_h[k];
-    else if (cg.type == 6) for (int k = 0; k < 3; ++k) h[k] = cg.size[k];
-    else { h[0] = h[1] = cg.size[0]; h[2] = cg.size[0] + cg.size[1]; }
-    P.chk.gvert[g][0] = cg.vert_adr; P.chk.gvert[g][1] = cg.type == 7 ? cg.vert_num : 0;
-    P.chk.glink[g] = (int8_t)cg.link;
-    P.chk.gtype[g] = (int8_t)cg.type;
-  }
   return P;
 }
 
@@ -314,268 +245,43 @@ int upload_coll_classes(rcsh_sim* s) {
   return RCSH_OK;
 }
 
-// MuJoCo's pair filters on two collision geoms of the robot (mj_collision: different weld bodies -- here: links; no
-// parent-child pair unless one of the two is welded to the world), then what the callbacks make of a contact of the pair
-// (SimRobot.cpp:172-182: either geom is an arm collision geom; SimGripper.cpp:108-130: not finger-finger, either geom is a
-// gripper collision geom, geom[1] is not in the ignore list -- quirk Q6).  Pairs nobody reacts to are dropped.
-constexpr int kSelfStageVertsHost = 304;  // contact_team.h: kSelfStageVerts
-// all pairs MuJoCo's filters admit; `reacting_only`: drop those no collision callback reacts to (cls == 0)
-// A geom welded to the world against a geom of the arm's first link (MuJoCo's parent-child filter lets the pair through: the parent is
-// static): ONE hinge moves them relative to each other, and a rotation leaves every point's coordinate ALONG the hinge's axis alone.  If
-// the two geoms' extents along that axis do not overlap, no joint angle brings them into contact -- the pair is dropped from the tables
-// (the FR3's link 1 sits on link 0 with 0.1 mm between the hulls: the pair survived every bounding test in every pose, and the contact
-// phase refined it in every substep of every escalated environment).
-bool never_touch_across_first_hinge(const rcsh_sim* s, const ContactGeom& a, const ContactGeom& b) {
-  const ContactGeom* w = a.link < 0 ? &a : (b.link < 0 ? &b : nullptr);
-  const ContactGeom* l = a.link == 0 ? &a : (b.link == 0 ? &b : nullptr);
-  if (!w || !l || s->dm.jtype[0] == kSlide) return false;
-  const DevModel& m = s->dm;
-  double ax[3] = {m.axis[0][0], m.axis[0][1], m.axis[0][2]}, aw[3];
-  for (int k = 0; k < 3; ++k) aw[k] = m.rot0[0][3 * k] * ax[0] + m.rot0[0][3 * k + 1] * ax[1] + m.rot0[0][3 * k + 2] * ax[2];
-  auto extent = [&](const ContactGeom& g, const double* u, double& lo, double& hi) {
-    // of the geom along u, both in the frame of the geom's link
-    double ug[3];  // u in the geom's frame
-    for (int k = 0; k < 3; ++k) ug[k] = g.rot[k] * u[0] + g.rot[3 + k] * u[1] + g.rot[6 + k] * u[2];
-    const double c = u[0] * g.pos[0] + u[1] * g.pos[1] + u[2] * g.pos[2];
-    if (g.type == 7) {
-      lo = 1e300; hi = -1e300;
-      for (int v = 0; v < g.vert_num; ++v) {
-        const double* x = &s->cverts[3 * (size_t)(g.vert_adr + v)];
-        const double d = c + ug[0] * x[0] + ug[1] * x[1] + ug[2] * x[2];
-        lo = std::min(lo, d); hi = std::max(hi, d);
-      }
-    } else {
-      double e;
-      if (g.type == 6) e = std::fabs(ug[0]) * g.size[0] + std::fabs(ug[1]) * g.size[1] + std::fabs(ug[2]) * g.size[2];
-      else if (g.type == 3) e = std::fabs(ug[2]) * g.size[1] + g.size[0];
-      else e = g.size[0];
-      lo = c - e; hi = c + e;
-    }
-  };
-  double wlo, whi, llo, lhi;
-  extent(*w, aw, wlo, whi);
-  extent(*l, ax, llo, lhi);
-  const double off = aw[0] * m.pos0[0][0] + aw[1] * m.pos0[0][1] + aw[2] * m.pos0[0][2];
-  llo += off; lhi += off;
-  if (w->type == 7 && w->vert_num == 0) return false;
-  if (l->type == 7 && l->vert_num == 0) return false;
-  return llo - whi > 1e-7 || wlo - lhi > 1e-7;
-}
+static_assert(kSelfStageVertsHost == kSelfStageVerts, "the pair filter's vertex cap is the self-contact stage's LDS room (contact_team.h)");
 
-std::vector<SelfPair> list_geom_pairs(const rcsh_sim* s, bool reacting_only) {
-  std::vector<SelfPair> out;
-  const int ng = (int)s->cgeoms.size();
-  auto parent = [&](int link) { return link < s->narm ? link - 1 : s->narm - 1; };
-  for (int i = 0; i < ng; ++i)
-    for (int j = i + 1; j < ng; ++j) {
-      const ContactGeom &a = s->cgeoms[i], &b = s->cgeoms[j];
-      if (a.link == b.link) continue;
-      if (a.link >= 0 && b.link >= 0 && (parent(a.link) == b.link || parent(b.link) == a.link)) continue;
-      {
-        // MuJoCo's mask filter: the pair collides if (contype0 & conaffinity1) || (contype1 & conaffinity0) (advisor, round 4: pairs the
-        // masks exclude raised the sticky flags -- and, since round 5, would send an environment to the contact-resolving launch)
-        const auto& ct = s->hm.geom_contype;
-        const auto& ca = s->hm.geom_conaffinity;
-        if (a.geom_id < (int)ct.size() && b.geom_id < (int)ct.size() && a.geom_id < (int)ca.size() && b.geom_id < (int)ca.size() &&
-            !((ct[a.geom_id] & ca[b.geom_id]) || (ct[b.geom_id] & ca[a.geom_id])))
-          continue;
-      }
-      if ((a.type == 7 && a.vert_num == 0) || (b.type == 7 && b.vert_num == 0)) continue;  // mesh blob missing from the checkout
-      if (a.vert_num + b.vert_num > kSelfStageVertsHost) continue;  // (the contact table admits hulls of at most 152 vertices each: model.cpp build_contact_table)
-      if (never_touch_across_first_hinge(s, a, b)) continue;
-      const bool swap = a.type > b.type;  // geom[0] / geom[1] of the contact: by type, then by id (the table is in id order)
-      const ContactGeom &g0 = swap ? b : a, &g1 = swap ? a : b;
-      int cls = 0;
-      if ((g0.cls | g1.cls) & 1) cls |= 1;
-      if (!((g0.cls & 4) && (g1.cls & 4)) && ((g0.cls | g1.cls) & 16) && !(g1.cls & 8)) cls |= 2;
-      if (!cls && reacting_only) continue;
-      SelfPair pr{};
-      pr.g0 = (int16_t)(swap ? j : i); pr.g1 = (int16_t)(swap ? i : j);
-      pr.l0 = (int16_t)g0.link; pr.l1 = (int16_t)g1.link;
-      pr.cls = cls;
-      {
-        // joints on the tree path between the two links: root paths' symmetric difference (arm link i: joints 0..i; a finger:
-        // the whole arm and its own slide; welded to the world: none)
-        auto root_path = [&](int link) -> int {
-          if (link < 0) return 0;
-          if (link < s->narm) return (1 << (link + 1)) - 1;
-          return ((1 << s->narm) - 1) | (1 << link);
-        };
-        pr.joints = root_path(g0.link) ^ root_path(g1.link);
-      }
-      auto bounds = [](const ContactGeom& g, double* c, double& r, double* rot, double* h) {
-        // bounding box of the geom (geom frame: centre lc, half extents h), carried into the link frame
-        double lc[3] = {0, 0, 0};
-        if (g.type == 7) { for (int k = 0; k < 3; ++k) { lc[k] = g.aabb_c[k]; h[k] = g.aabb_h[k]; } }
-        else if (g.type == 6) { for (int k = 0; k < 3; ++k) h[k] = g.size[k]; }
-        else { h[0] = h[1] = g.size[0]; h[2] = g.size[0] + g.size[1]; }
-        for (int k = 0; k < 3; ++k) c[k] = g.rot[3 * k] * lc[0] + g.rot[3 * k + 1] * lc[1] + g.rot[3 * k + 2] * lc[2] + g.pos[k];
-        for (int k = 0; k < 9; ++k) rot[k] = g.rot[k];
-        r = std::sqrt(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
-      };
-      bounds(g0, pr.c0, pr.r0, pr.rot0, pr.h0);
-      bounds(g1, pr.c1, pr.r1, pr.rot1, pr.h1);
-      out.push_back(pr);
-    }
-  return out;
+// one buffer, grown on demand: the stream may still be reading or writing the old one
+int grow(rcsh_sim* s, Grown& g, size_t bytes, bool pinned) {
+  if (bytes <= g.cap) return RCSH_OK;
+  if (g.p) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    void* old = g.p;
+    g = Grown{};
+    HIP_TRY(pinned ? hipHostFree(old) : hipFree(old));
+  }
+  void* p = nullptr;
+  HIP_TRY(pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes));
+  g.p = p; g.cap = bytes;
+  return RCSH_OK;
 }
-void build_self_pairs(rcsh_sim* s) {
-  s->pairs.clear();
-  if (std::getenv("RCSH_DEBUG_NO_SELF_PAIRS")) return;  // development switch: what the pair tests cost
-  s->pairs = list_geom_pairs(s, true);
-}
+int grow_device(rcsh_sim* s, Grown& g, size_t bytes) { return grow(s, g, bytes, false); }
+int grow_pinned(rcsh_sim* s, Grown& g, size_t bytes) { return grow(s, g, bytes, true); }
 
-// The tables of the end-of-launch check for contacts nobody resolves (check_team.h): ALL admitted geom pairs (full records for the
-// box test and the narrow phase, packed entries for the sphere test).  Pairs of the same two bodies stay together, so that a
-// cluster of pairs that come near at once (the two fingers' pads when the gripper closes) spreads over the lanes.
-void build_check_table(rcsh_sim* s) {
-  s->chk_pairs = list_geom_pairs(s, false);
-  auto key = [](const SelfPair& p) { const int a = std::min(p.l0, p.l1) + 1, b = std::max(p.l0, p.l1) + 1; return a * 64 + b; };
-  std::stable_sort(s->chk_pairs.begin(), s->chk_pairs.end(), [&](const SelfPair& x, const SelfPair& y) { return key(x) < key(y); });
-  s->chk_ent.clear();
-  for (const auto& p : s->chk_pairs) {
-    CheckEntry e{};
-    // (bits 16-23: 1 + the deepest link both geoms' links descend from or are -- 0: none, the world; the slack test charges each geom
-    // with the joints below it)
-    int ca = -1;
-    {
-      const int na = s->narm;
-      auto parent = [&](int link) { return link < na ? link - 1 : na - 1; };
-      auto is_anc = [&](int a, int l) { for (int k = l; k >= 0; k = parent(k)) if (k == a) return true; return false; };
-      for (int k = p.l0; k >= 0 && ca < 0; k = parent(k)) if (p.l1 >= 0 && is_anc(k, p.l1)) ca = k;
-    }
-    e.geoms = (uint32_t)p.g0 | ((uint32_t)p.g1 << 8) | ((uint32_t)(ca + 1) << 16);
-    e.rsum = (float)(p.r0 + p.r1) * 1.000001f + 2e-6f;  // (single-precision centres: the sum of the radii rounded up)
-    s->chk_ent.push_back(e);
-  }
-  // the geoms' bounding boxes in their links' frames (what SelfPair carries per pair, once per geom)
-  s->chk_geoms.clear();
-  for (const auto& cg : s->cgeoms) {
-    CheckGeom g{};
-    double lc[3] = {0, 0, 0};
-    if (cg.type == 7) for (int k = 0; k < 3; ++k) lc[k] = cg.aabb_c[k];
-    for (int k = 0; k < 3; ++k) g.c[k] = cg.rot[3 * k] * lc[0] + cg.rot[3 * k + 1] * lc[1] + cg.rot[3 * k + 2] * lc[2] + cg.pos[k];
-    for (int k = 0; k < 9; ++k) g.rot[k] = cg.rot[k];
-    s->chk_geoms.push_back(g);
-  }
-}
-
-// lever[j]: how far one radian of hinge j (one metre of a slide) can move a point of any collision geom downstream of it.
-// Distances between consecutive joint anchors are constants of the links; a finger's anchor slides, so its stroke is added.
-// The additive slack of every hinge lever below (metres per radian, on top of the 1 % factor).  A chain from a hinge to a geom holds
-// at most one slide, whose stroke the lever includes: so the levers also hold for a slide up to kLeverSlack PAST its stroke.  The
-// collision guard leans on that (guard_launch: kGuardSlideTol).
-constexpr double kLeverSlack = 1e-3;
-void build_self_levers(rcsh_sim* s) {
-  const DevModel& m = s->dm;
-  const int na = s->narm, nl = s->nl;
-  auto parent = [&](int link) { return link < na ? link - 1 : na - 1; };
-  // reach[L]: from link L's joint anchor to the farthest point of a collision geom ON link L (link frame)
-  std::vector<double> reach(nl, 0.0), hop(nl, 0.0), stroke(nl, 0.0);
-  for (const auto& g : s->cgeoms) {
-    if (g.link < 0) continue;
-    double c[3], h[3] = {g.size[0], g.size[1], g.size[2]}, lc[3] = {0, 0, 0};
-    if (g.type == 7) for (int k = 0; k < 3; ++k) { lc[k] = g.aabb_c[k]; h[k] = g.aabb_h[k]; }
-    else if (g.type == 3) { h[0] = h[1] = g.size[0]; h[2] = g.size[0] + g.size[1]; }
-    for (int k = 0; k < 3; ++k) c[k] = g.rot[3 * k] * lc[0] + g.rot[3 * k + 1] * lc[1] + g.rot[3 * k + 2] * lc[2] + g.pos[k] - m.jpos[g.link][k];
-    const double r = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) + std::sqrt(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
-    reach[g.link] = std::max(reach[g.link], r);
-  }
-  for (int L = 0; L < nl; ++L) {
-    // hop[L]: from the parent link's anchor to link L's anchor (parent link frame, at qpos0; a hinge's anchor does not move)
-    const int p = parent(L);
-    double a[3];
-    for (int k = 0; k < 3; ++k) a[k] = m.pos0[L][k] + m.rot0[L][3 * k] * m.jpos[L][0] + m.rot0[L][3 * k + 1] * m.jpos[L][1] + m.rot0[L][3 * k + 2] * m.jpos[L][2] - (p >= 0 ? m.jpos[p][k] : 0.0);
-    hop[L] = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    if (m.jtype[L] == kSlide) stroke[L] = std::max(std::fabs(m.range[L][0] - m.qpos0[L]), std::fabs(m.range[L][1] - m.qpos0[L]));
-  }
-  // far[L]: from link L's anchor to the farthest geom point on L or downstream of it
-  std::vector<double> far(nl, 0.0);
-  for (int L = nl - 1; L >= 0; --L) {
-    far[L] = std::max(far[L], reach[L] + stroke[L]);
-    const int p = parent(L);
-    if (p >= 0) far[p] = std::max(far[p], hop[L] + stroke[L] + far[L]);
-  }
-  for (int j = 0; j < 12; ++j) s->self_lever[j] = 0.0;
-  for (int j = 0; j < nl; ++j) s->self_lever[j] = m.jtype[j] == kSlide ? 1.0 : 1.01 * far[j] + kLeverSlack;
-  // link_lever[j][l]: the same bound for the geoms ON link l alone (j an ancestor-or-self joint of l) -- what the contact phase's slack
-  // test charges a geom pair / a geom above the floor with.  The isotropic lever above takes the whole arm's reach for joint 1; the pair
-  // (link 0, link 2), whose hulls stay a centimetre apart in every pose, sits 0.2 m from that axis: charged with 1.2 m per radian it was
-  // due in nearly every substep, and with it the whole collision pass.
-  for (int k = 0; k < 144 + 12 * 32; ++k) s->link_lever[k] = 0.0f;
-  for (int l = 0; l < nl; ++l) {
-    double acc = reach[l];  // from link l's anchor to the farthest point of a geom on l
-    for (int j = l; j >= 0; j = parent(j)) {
-      // acc: from joint j's anchor to the farthest point of a geom on l, over every configuration of the joints in between
-      s->link_lever[j * 12 + l] = (float)(m.jtype[j] == kSlide ? 1.0 : (1.01 * (acc + stroke[l]) + kLeverSlack) * 1.000001);
-      acc += hop[j] + stroke[j];
-    }
-  }
-  // ... and per GEOM (kLevGeom + j * 32 + g): the same bound for the points of geom g alone.  A link's lever is its farthest geom's: link 7
-  // carries the flange's hull AND the hand's, 0.2 m from its joint, and the pair (link 5's hull, the flange's hull) -- 14-17 mm apart in
-  // every pose -- was charged the hand's reach: in step_until_convergence, whose launches move a joint by up to five degrees, its
-  // certificate failed in a third of the batch at every step (check_team.h: the narrow phase's second chance).
-  static_assert(kMaxCGeom <= 32, "a column per collision geom");
-  for (size_t gi = 0; gi < s->cgeoms.size() && gi < 32; ++gi) {
-    const auto& g = s->cgeoms[gi];
-    if (g.link < 0) continue;
-    double c[3], h[3] = {g.size[0], g.size[1], g.size[2]}, lc[3] = {0, 0, 0};
-    if (g.type == 7) for (int k = 0; k < 3; ++k) { lc[k] = g.aabb_c[k]; h[k] = g.aabb_h[k]; }
-    else if (g.type == 3) { h[0] = h[1] = g.size[0]; h[2] = g.size[0] + g.size[1]; }
-    for (int k = 0; k < 3; ++k) c[k] = g.rot[3 * k] * lc[0] + g.rot[3 * k + 1] * lc[1] + g.rot[3 * k + 2] * lc[2] + g.pos[k] - m.jpos[g.link][k];
-    double acc = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) + std::sqrt(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
-    const int l = g.link;
-    // (the geom's OWN hinge: what a radian of it moves is a point's distance from the AXIS, not from the anchor -- the largest over the
-    // eight corners of the geom's box; a flange that is a cylinder about its joint's axis: its radius instead of its length)
-    double radial = 0.0;
-    for (int corner = 0; corner < 8; ++corner) {
-      const double sg[3] = {corner & 1 ? h[0] : -h[0], corner & 2 ? h[1] : -h[1], corner & 4 ? h[2] : -h[2]};
-      double v[3];
-      for (int k = 0; k < 3; ++k) v[k] = c[k] + g.rot[3 * k] * sg[0] + g.rot[3 * k + 1] * sg[1] + g.rot[3 * k + 2] * sg[2];
-      const double* ax = m.axis[l];
-      const double an = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-      const double al = an > 0 ? (v[0] * ax[0] + v[1] * ax[1] + v[2] * ax[2]) / an : 0.0;
-      const double r2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2] - al * al;
-      radial = std::max(radial, std::sqrt(std::max(r2, 0.0)));
-    }
-    for (int j = l; j >= 0; j = parent(j)) {
-      const double arm = j == l && m.jtype[j] != kSlide ? std::min(radial, acc) : acc + stroke[l];
-      s->link_lever[144 + j * 32 + (int)gi] = (float)(m.jtype[j] == kSlide ? 1.0 : (1.01 * arm + kLeverSlack) * 1.000001);
-      acc += hop[j] + stroke[j];
-    }
-  }
+// a host table's device copy; the buffer grows on demand (grow_device waits for the stream before it frees one a launch may still read)
+int upload(rcsh_sim* s, Grown& g, const void* src, size_t bytes) {
+  if (int rc = grow_device(s, g, bytes)) return rc;
+  if (bytes) HIP_TRY(hipMemcpyAsync(g.p, src, bytes, hipMemcpyHostToDevice, s->stream));
+  return RCSH_OK;
 }
 
 int upload_contact_table(rcsh_sim* s) {
+  CollisionTables& t = s->tables;
+  build_collision_tables(s->hm, s->dm, s->cp, s->cgeoms, s->cverts, t);
+  if (std::getenv("RCSH_DEBUG_NO_SELF_PAIRS")) { t.pairs.clear(); t.ctab.npair = 0; }  // development switch: what the pair tests cost
   if (s->cgeoms.empty()) return RCSH_OK;
-  build_self_pairs(s);
-  build_self_levers(s);
-  if (s->d_pairs) { HIP_TRY(hipStreamSynchronize(s->stream)); HIP_TRY(hipFree(s->d_pairs)); s->d_pairs = nullptr; }
-  if (!s->pairs.empty()) {
-    HIP_TRY(hipMalloc(&s->d_pairs, sizeof(SelfPair) * s->pairs.size()));
-    HIP_TRY(hipMemcpyAsync(s->d_pairs, s->pairs.data(), sizeof(SelfPair) * s->pairs.size(), hipMemcpyHostToDevice, s->stream));
-  }
-  build_check_table(s);
-  if (s->d_chk_ent) { HIP_TRY(hipStreamSynchronize(s->stream)); HIP_TRY(hipFree(s->d_chk_ent)); s->d_chk_ent = nullptr; }
-  if (s->d_chk_geoms) { HIP_TRY(hipFree(s->d_chk_geoms)); s->d_chk_geoms = nullptr; }
-  // (a scene with more admitted pairs than a lane keeps entries for is NOT refused -- plain Sim.step users never read the flag --: the
-  // pairs past the capacity stay unchecked, counted and reported: rcsh_sim_contact_check_unchecked_pairs; advisor, round 4)
-  s->chk_unchecked = 0;
-  if ((int)s->chk_ent.size() > kMaxCheckPairs) {
-    s->chk_unchecked = (int)s->chk_ent.size() - kMaxCheckPairs;
-    s->chk_ent.resize(kMaxCheckPairs);
-    s->chk_pairs.resize(kMaxCheckPairs);
-  }
-  if (!s->chk_ent.empty()) {
-    HIP_TRY(hipMalloc(&s->d_chk_ent, sizeof(CheckEntry) * s->chk_ent.size()));
-    HIP_TRY(hipMemcpyAsync(s->d_chk_ent, s->chk_ent.data(), sizeof(CheckEntry) * s->chk_ent.size(), hipMemcpyHostToDevice, s->stream));
-  }
-  if (!s->d_lev) HIP_TRY(hipMalloc(&s->d_lev, sizeof(s->link_lever)));
-  HIP_TRY(hipMemcpyAsync(s->d_lev, s->link_lever, sizeof(s->link_lever), hipMemcpyHostToDevice, s->stream));
-  if (!s->chk_geoms.empty()) {
-    HIP_TRY(hipMalloc(&s->d_chk_geoms, sizeof(CheckGeom) * s->chk_geoms.size()));
-    HIP_TRY(hipMemcpyAsync(s->d_chk_geoms, s->chk_geoms.data(), sizeof(CheckGeom) * s->chk_geoms.size(), hipMemcpyHostToDevice, s->stream));
-  }
+  int rc = upload(s, s->d_pairs, t.pairs.data(), sizeof(SelfPair) * t.pairs.size());
+  if (!rc) rc = upload(s, s->d_chk_ent, t.chk_ent.data(), sizeof(CheckEntry) * t.chk_ent.size());
+  if (!rc) rc = upload(s, s->d_chk_geoms, t.chk_geoms.data(), sizeof(CheckGeom) * t.chk_geoms.size());
+  if (rc) return rc;
+  if (!s->d_lev) HIP_TRY(hipMalloc(&s->d_lev, sizeof(t.link_lever)));
+  HIP_TRY(hipMemcpyAsync(s->d_lev, t.link_lever, sizeof(t.link_lever), hipMemcpyHostToDevice, s->stream));
   if (!s->d_cgeoms) HIP_TRY(hipMalloc(&s->d_cgeoms, sizeof(ContactGeom) * s->cgeoms.size()));
   HIP_TRY(hipMemcpyAsync(s->d_cgeoms, s->cgeoms.data(), sizeof(ContactGeom) * s->cgeoms.size(), hipMemcpyHostToDevice, s->stream));
   if (!s->d_cverts && !s->cverts.empty()) {
@@ -670,7 +376,7 @@ int launch_run_once(rcsh_sim* s, const RunOp& op_in, bool timed) {
   // finalisation and the shared math.)
   // DET: launches that run the collision callbacks (step_until_convergence) of a model with collision geoms carry the
   // contact detection of the position stage; Sim::step(k) never looks at the flags (sim.cpp:108-115)
-  const bool det = op.nsteps < 0 && (P.coll.has_plane || !s->pairs.empty());
+  const bool det = op.nsteps < 0 && (P.coll.has_plane || !s->tables.pairs.empty());
   // per-environment escalation: stepping launches of a box-less scene whose robot contacts are resolved environment by environment
   const bool esc = s->esc_mode && s->box.resolve && !s->box.present && (op.nsteps != 0 || op.do_reset) && !op.observe_only;
   if (esc) {
@@ -784,23 +490,6 @@ int fits(int width, int slice_width, const char* what) {
   if (width < 0 || width > slice_width) return fail(RCSH_ERR_ARG, std::string(what) + ": wider than its staging slice");
   return RCSH_OK;
 }
-
-// one buffer, grown on demand: the stream may still be reading or writing the old one
-int grow(rcsh_sim* s, Grown& g, size_t bytes, bool pinned) {
-  if (bytes <= g.cap) return RCSH_OK;
-  if (g.p) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    void* old = g.p;
-    g = Grown{};
-    HIP_TRY(pinned ? hipHostFree(old) : hipFree(old));
-  }
-  void* p = nullptr;
-  HIP_TRY(pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes));
-  g.p = p; g.cap = bytes;
-  return RCSH_OK;
-}
-int grow_device(rcsh_sim* s, Grown& g, size_t bytes) { return grow(s, g, bytes, false); }
-int grow_pinned(rcsh_sim* s, Grown& g, size_t bytes) { return grow(s, g, bytes, true); }
 
 // The device staging's layout: every slice's place and width is decided here, from n and the model's widths.  Called twice: without
 // a base for the size, then with the allocation.
@@ -1077,7 +766,7 @@ void rcsh_sim_destroy(rcsh_sim* s) {
   if (s->order_ev) hipEventDestroy(s->order_ev);
   for (auto e : s->ev_stop) hipEventDestroy(e);
   hipFree(s->d_model); hipFree(s->d_coll_xyzr); hipFree(s->d_coll_cls); hipFree(s->S); hipFree(s->flags); hipFree(s->conv);
-  hipFree(s->d_cgeoms); hipFree(s->d_cverts); hipFree(s->d_pairs); hipFree(s->d_chk_geoms); hipFree(s->d_chk_ent); hipFree(s->d_lev);
+  hipFree(s->d_cgeoms); hipFree(s->d_cverts); hipFree(s->d_pairs.p); hipFree(s->d_chk_geoms.p); hipFree(s->d_chk_ent.p); hipFree(s->d_lev);
   hipFree(s->d_slack);
   hipFree(s->d_query.p);
   hipFree(s->d_guard);
@@ -1420,7 +1109,7 @@ int query_check(rcsh_sim* s, int32_t m, int32_t kinds, const double* free_qpos) 
   if (kinds & ~kQueryKinds) return fail(RCSH_ERR_ARG, "unknown bit in the kinds mask (bit 0 floor, 1 self, 2 free body)");
   if (free_qpos && !s->box.present) return fail(RCSH_ERR_ARG, "free_qpos given in a scene without a free body");
   if (!s->cgeoms_dropped.empty()) return fail(RCSH_ERR_MODEL, "collision geoms beyond the contact table's capacity: the answer could not be exact");
-  if (s->chk_unchecked > 0) return fail(RCSH_ERR_MODEL, "admitted geom pairs beyond the check's table: the answer could not be exact");
+  if (s->tables.chk_unchecked > 0) return fail(RCSH_ERR_MODEL, "admitted geom pairs beyond the check's table: the answer could not be exact");
   for (int g = 0; g < s->hm.ngeom; ++g) {
     // (the contact table holds capsules, boxes and convex meshes; a colliding geom of another type would be left out silently)
     const int ty = s->hm.geom_type[g];
@@ -1455,7 +1144,7 @@ QueryArgs query_args(rcsh_sim* s, int32_t m, int32_t kinds) {
   }
   for (int k = 0; k < 3; ++k) A.box_size[k] = s->box.size[k];
   for (int L = 0; L < 12; ++L) {
-    // (build_self_levers: a slide's lever holds over qpos0 -+ its stroke)
+    // (model.cpp build_self_levers: a slide's lever holds over qpos0 -+ its stroke)
     const bool slide = L < s->nl && s->dm.jtype[L] == kSlide;
     const double stroke = slide ? std::max(std::fabs(s->dm.range[L][0] - s->dm.qpos0[L]), std::fabs(s->dm.range[L][1] - s->dm.qpos0[L])) : HUGE_VAL;
     A.slide_lo[L] = slide ? s->dm.qpos0[L] - stroke : -HUGE_VAL;
@@ -1854,7 +1543,7 @@ int rcsh_sim_set_contact_check(rcsh_sim* s, int32_t every) {
 int rcsh_sim_contact_check_unchecked_pairs(rcsh_sim* s, int32_t* count) {
   REQUIRE_SIM(s);
   if (!count) return fail(RCSH_ERR_ARG, "count is null");
-  *count = s->chk_unchecked;
+  *count = s->tables.chk_unchecked;
   return RCSH_OK;
 }
 int rcsh_sim_contact_table_dropped(rcsh_sim* s, int32_t* geom_ids, int32_t capacity, int32_t* count, char* reason, size_t reason_capacity) {
@@ -2016,7 +1705,7 @@ int guard_launch(rcsh_sim* s, const double* action_dev, int32_t* result, double*
   G.Q.resolution = s->guard.resolution;
   // A finger of the open hand rests ON its joint limit, and the soft limit lets it through by some 10 um (measured: up to 44 um in a
   // rollout): for the motion query such a row has left the stroke the levers were built for and is never certified -- the guard
-  // would block a quarter of a batch for it.  The levers hold further than the query admits: build_self_levers charges a hinge
+  // would block a quarter of a batch for it.  The levers hold further than the query admits: model.cpp build_self_levers charges a hinge
   // 1.01 (d + stroke) + kLeverSlack for a geom whose distance bound is d + stroke, and a chain holds one slide, so a slide up to
   // kLeverSlack past its stroke is covered by that additive term alone.  The guard admits half of it.
   constexpr double kGuardSlideTol = 5e-4;
@@ -3098,8 +2787,8 @@ extern "C" int rcsh_debug_check_cycles(unsigned long long* out16, int clear) {
   return 0;
 }
 extern "C" int rcsh_debug_check_pairs(rcsh_sim* s, int32_t* g0g1 /* [cap][2] */, int32_t cap, int32_t* n, int32_t* nb) {
-  *n = (int)s->chk_pairs.size(); *nb = 0;
-  for (int i = 0; i < *n && i < cap; ++i) { g0g1[2 * i] = s->cgeoms[s->chk_pairs[i].g0].geom_id; g0g1[2 * i + 1] = s->cgeoms[s->chk_pairs[i].g1].geom_id; }
+  *n = (int)s->tables.chk_pairs.size(); *nb = 0;
+  for (int i = 0; i < *n && i < cap; ++i) { g0g1[2 * i] = s->cgeoms[s->tables.chk_pairs[i].g0].geom_id; g0g1[2 * i + 1] = s->cgeoms[s->tables.chk_pairs[i].g1].geom_id; }
   return 0;
 }
 #endif

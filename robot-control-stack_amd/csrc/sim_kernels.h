@@ -237,17 +237,6 @@ __device__ __forceinline__ void esc_finish(const RunOp& op, int n) {
   if ((threadIdx.x & 63u) == 63) { op.esc_ctr[1] = (uint32_t)count; op.esc_ctr[0] = 0; op.esc_ctr[2] = 0; }
 }
 
-// Contact detection against the scene's static plane (flags only): sample points of the collision geoms, link frame
-struct CollTable {
-  const double* xyzr;      // [npts][4]
-  const uint8_t* cls;      // [npts] bit 0: geom is one of SimRobot's arm collision geoms; bit 1: SimGripper's
-  int32_t link_adr[kMaxLinks + 1];
-  double link_sphere[kMaxLinks][4];  // broad phase: bounding sphere of the link's points (link frame)
-  double link_aabb[kMaxLinks][6];    // broad phase of the contact phase: bounding box of the link's points (centre, half extents)
-  int32_t has_plane, has_static;     // has_static: link_aabb[NL] bounds collision geoms welded to the world (world frame)
-  double plane_n[3], plane_d;
-};
-
 // Rendering callbacks (reference Sim::invoke_rendering_callbacks, src/sim/sim.cpp:63-81,108-115): cameras with a frame rate are
 // due after a substep when more than 1 / frame_rate of simulated time has passed since their last frame.  A kernel cannot
 // call the renderer, so the substep loop RECORDS what the renderer would have seen -- the qpos of that substep's position

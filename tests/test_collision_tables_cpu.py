@@ -1,0 +1,284 @@
+"""The collision tables (csrc/model.cpp: build_collision_tables) on the CPU: which geom pairs exist, the records of the contact phase
+and of the end-of-launch certificate, and the levers every slack test, the certificate, the motion query and the collision guard rest
+on.  A lever that is too small lets the certificate pass a contact it should have caught, and nothing on the device reports it.
+
+The builder runs in a stand-alone program (tests/host/collision_tables_main.cpp, compiled here with g++ together with model.cpp; the
+scene comes from tools/export_model_c.py) that prints the tables as JSON: nothing of it is loaded into this process.  What the tables
+are held against is worked out in numpy from the compiled scene's arrays (rcs_amd.mjcf) alone."""
+import json
+import os
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "robot-control-stack_amd")
+CSRC = os.path.join(PKG, "csrc")
+sys.path[:0] = [PKG]
+
+from rcs_amd.envs import utils  # noqa: E402
+from rcs_amd.mjcf import compile_mjcf  # noqa: E402
+
+SCENES = ("fr3_empty_world", "xarm7_pick_world")
+N_CONFIGS = 200
+# what the forward kinematics below can be off by: a point a metre from the base through a chain of a dozen frame products in double
+# precision is good to ~1e-14 m; a displacement is the difference of two.  (A slide's lever is exactly 1: |displacement| = |delta| up to this.)
+FK_ROUNDING = 1e-13
+
+
+def _scene_xml(scene):
+    return os.path.join(PKG, "rcs_amd", "scenes", scene, "scene.xml")
+
+
+@pytest.fixture(scope="module")
+def built(tmp_path_factory):
+    """{scene: the program's JSON}, the builder compiled once."""
+    cxx = shutil.which(os.environ.get("CXX", "g++"))
+    assert cxx, "no host C++ compiler"
+    d = tmp_path_factory.mktemp("collision_tables")
+    obj = str(d / "model.o")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-c", os.path.join(CSRC, "model.cpp"), "-o", obj])
+    out = {}
+    for scene in SCENES:
+        sd = d / scene
+        sd.mkdir()
+        inc = subprocess.check_output([sys.executable, os.path.join(ROOT, "tools", "export_model_c.py"), _scene_xml(scene)], text=True)
+        (sd / "model.inc").write_text(inc)
+        prog = str(sd / "collision_tables")
+        subprocess.check_call([cxx, "-std=c++17", "-O1", f"-I{sd}", f"-I{CSRC}", os.path.join(ROOT, "tests", "host", "collision_tables_main.cpp"), obj, "-o", prog])
+        out[scene] = json.loads(subprocess.check_output([prog], text=True))
+    return out
+
+
+class Scene:
+    """The compiled scene's arrays and what follows from them by walking the body tree."""
+
+    def __init__(self, scene):
+        self.cm = cm = compile_mjcf(_scene_xml(scene))
+        self.A = A = {k: np.asarray(v) for k, v in cm.arrays.items()}
+        if scene == "xarm7_pick_world":
+            rcfg, gcfg = utils.xarm7_pick_sim_robot_cfg(), utils.xarm7_pick_sim_gripper_cfg()
+        else:
+            rcfg, gcfg = utils.default_sim_robot_cfg(), utils.default_sim_gripper_cfg()
+        ids = lambda names: {cm.name2id("geom", n) for n in names}  # noqa: E731
+        self.arm, self.grp, self.fing, self.ign = ids(rcfg.arm_collision_geoms), ids(gcfg.collision_geoms), ids(gcfg.collision_geoms_fingers), ids(gcfg.ignored_collision_geoms)
+        assert -1 not in self.arm | self.grp | self.fing | self.ign
+        assert set(A["jnt_type"].tolist()) <= {2, 3}  # hinges and slides, one per body: joint j is link j
+        self.nbody, self.njnt = int(cm.nbody), int(cm.njnt)
+        self.joint_of_body = {int(b): j for j, b in enumerate(A["jnt_bodyid"])}
+        assert len(self.joint_of_body) == self.njnt
+
+    def link_of_body(self, b):
+        """the joint of the nearest body at or above b that has one; -1: welded to the world"""
+        while b > 0:
+            if b in self.joint_of_body:
+                return self.joint_of_body[b]
+            b = int(self.A["body_parentid"][b])
+        return -1
+
+    def root_path(self, link):
+        """the links from `link` up to the root, `link` first"""
+        path = []
+        while link >= 0:
+            path.append(link)
+            link = self.link_of_body(int(self.A["body_parentid"][int(self.A["jnt_bodyid"][link])]))
+        return path
+
+    def parent_link(self, link):
+        p = self.root_path(link)
+        return p[1] if len(p) > 1 else -1
+
+    def geom_points(self, g):
+        """geom frame: the hull's vertices; a box's corners; the corners of the box (r, r, r + half length) around a capsule"""
+        A = self.A
+        t, sz = int(A["geom_type"][g]), A["geom_size"][g]
+        if t == 7:
+            return A["mesh_vert"][int(A["geom_vertadr"][g]):int(A["geom_vertadr"][g]) + int(A["geom_vertnum"][g])].reshape(-1, 3)
+        h = sz[:3] if t == 6 else np.array([sz[0], sz[0], sz[0] + sz[1]])
+        return np.array([[sx * h[0], sy * h[1], sz_ * h[2]] for sx in (-1, 1) for sy in (-1, 1) for sz_ in (-1, 1)])
+
+    def box_corners(self, g):
+        p = self.geom_points(g)
+        if len(p) == 0:
+            return p
+        lo, hi = p.min(axis=0), p.max(axis=0)
+        return np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])])
+
+    def fk(self, q):
+        """mj_kinematics in numpy, batched: q [N, njnt] -> body frames (xpos [N, nbody, 3], xmat [N, nbody, 3, 3])"""
+        A, N = self.A, len(q)
+        xpos, xmat = np.zeros((N, self.nbody, 3)), np.tile(np.eye(3), (N, self.nbody, 1, 1))
+        for b in range(1, self.nbody):
+            p = int(A["body_parentid"][b])
+            pos = xpos[:, p] + np.einsum("nij,j->ni", xmat[:, p], A["body_pos"][b])
+            R = xmat[:, p] @ _quat_mat(A["body_quat"][b])
+            if b in self.joint_of_body:
+                j = self.joint_of_body[b]
+                dq = q[:, j] - A["qpos0"][j]
+                axis = np.einsum("nij,j->ni", R, A["jnt_axis"][j])
+                if int(A["jnt_type"][j]) == 2:
+                    pos = pos + axis * dq[:, None]
+                else:
+                    anchor = pos + np.einsum("nij,j->ni", R, A["jnt_pos"][j])
+                    R = _axis_angle(axis, dq) @ R
+                    pos = anchor - np.einsum("nij,j->ni", R, A["jnt_pos"][j])
+            xpos[:, b], xmat[:, b] = pos, R
+        return xpos, xmat
+
+    def world_points(self, g, pts, xpos, xmat):
+        A, b = self.A, int(self.A["geom_bodyid"][g])
+        local = A["geom_pos"][g] + pts @ _quat_mat(A["geom_quat"][g]).T  # body frame
+        return xpos[:, b, None, :] + np.einsum("nij,pj->npi", xmat[:, b], local)
+
+
+def _quat_mat(q):
+    w, x, y, z = q / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _axis_angle(axis, angle):
+    """Rodrigues, batched: axis [N, 3] (unit), angle [N]"""
+    axis = axis / np.linalg.norm(axis, axis=1, keepdims=True)
+    K = np.zeros((len(angle), 3, 3))
+    K[:, 0, 1], K[:, 0, 2], K[:, 1, 0], K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -axis[:, 2], axis[:, 1], axis[:, 2], -axis[:, 0], -axis[:, 1], axis[:, 0]
+    s, c = np.sin(angle)[:, None, None], np.cos(angle)[:, None, None]
+    return np.eye(3) + s * K + (1 - c) * (K @ K)
+
+
+@pytest.fixture(scope="module")
+def scenes():
+    return {s: Scene(s) for s in SCENES}
+
+
+@pytest.mark.parametrize("scene", SCENES)
+@pytest.mark.parametrize("fingers", ["inside their stroke", "half the levers' slack past it"])
+def test_levers_bound_what_a_joint_moves(built, scenes, scene, fingers):
+    """For 200 random configurations, every joint j and every collision geom g downstream of it: moving j alone by +-delta (1e-3 rad, 1e-4 m
+    for a slide) displaces no corner of g's box and no vertex of its hull by more than the per-geom lever, the per-link lever or the
+    per-joint lever times |delta|.  Once with the fingers inside their stroke, once 0.5 kLeverSlack beyond it (the collision guard admits
+    that much: csrc/rcs_hip.hip guard_launch).  No (configuration, joint, geom) triple is left out."""
+    T, S = built[scene], scenes[scene]
+    A, nj = S.A, S.njnt
+    table_index = {g["geom_id"]: i for i, g in enumerate(T["geoms"])}
+    rng = np.random.default_rng(7)
+    lo, hi = A["jnt_range"][:, 0], A["jnt_range"][:, 1]
+    assert A["jnt_limited"].all()
+    q = rng.uniform(lo, hi, size=(N_CONFIGS, nj))
+    slides = np.flatnonzero(A["jnt_type"] == 2)
+    assert len(slides) == 2
+    if fingers != "inside their stroke":
+        past = 0.5 * T["lever_slack"]
+        for j in slides:
+            q[:, j] = np.where(rng.integers(0, 2, N_CONFIGS) == 1, hi[j] + past, lo[j] - past)
+    lev = np.array(T["link_lever"])
+    base = S.fk(q)
+    downstream = {j: [g for g in table_index if j in S.root_path(S.link_of_body(int(A["geom_bodyid"][g])))] for j in range(nj)}
+    expected = N_CONFIGS * sum(len(v) for v in downstream.values())
+    assert expected > N_CONFIGS * 50
+    checked, worst = 0, 0.0
+    for j in range(nj):
+        delta = 1e-4 if int(A["jnt_type"][j]) == 2 else 1e-3
+        moved = []
+        for sign in (1.0, -1.0):
+            qm = q.copy()
+            qm[:, j] += sign * delta
+            moved.append(S.fk(qm))
+        for g in downstream[j]:
+            gi = table_index[g]
+            pts = np.concatenate([S.box_corners(g), S.geom_points(g)]) if len(S.geom_points(g)) else np.zeros((1, 3))
+            p0 = S.world_points(g, pts, *base)
+            disp = np.maximum.reduce([np.linalg.norm(S.world_points(g, pts, *m) - p0, axis=2).max(axis=1) for m in moved])
+            link = T["geoms"][gi]["link"]
+            assert link == S.link_of_body(int(A["geom_bodyid"][g]))
+            bounds = (lev[T["lev_geom"] + j * 32 + gi], lev[j * 12 + link], T["self_lever"][j])
+            for name, b in zip(("geom", "link", "joint"), bounds):
+                print(f"{scene} joint {j} geom {g}: displacement / |delta| <= {disp.max() / delta:.6f}; {name} lever {b:.6f}")
+                assert (disp <= b * delta + FK_ROUNDING).all(), (scene, j, g, name, disp.max() / delta, b)
+                worst = max(worst, disp.max() / (b * delta))
+            checked += N_CONFIGS
+    assert checked == expected  # the share of triples skipped is zero
+    assert 0.5 < worst <= 1.0 + 1e-8  # (and the bounds are not vacuous: some lever is used to more than half)
+
+
+@pytest.mark.parametrize("scene", SCENES)
+def test_the_pair_set_is_what_the_filters_say(built, scenes, scene):
+    """MuJoCo's filters restated over the scene's arrays: different links, not parent and child unless one is welded to the world, the
+    contype / conaffinity mask; then the vertex cap of the self-contact stage and no hull without its mesh.  The check's pairs are that
+    set minus exactly what never_touch_across_first_hinge drops (the FR3: link 0's hull against link 1's, 0.1 mm apart in every pose:
+    tests/test_contacts_cpu.py::test_link0_and_link1_never_touch_over_joint_1s_range); the contact phase's pairs are those a collision
+    callback reacts to; entries are sorted by body pair; the common ancestor and the joints between the links are a walk up the tree."""
+    T, S = built[scene], scenes[scene]
+    A = S.A
+    geoms = [g for g in range(int(S.cm.ngeom)) if int(A["geom_type"][g]) in (3, 6, 7) and (A["geom_contype"][g] or A["geom_conaffinity"][g])]
+    assert [g["geom_id"] for g in T["geoms"]] == geoms
+    link = {g: S.link_of_body(int(A["geom_bodyid"][g])) for g in geoms}
+    nvert = {g: int(A["geom_vertnum"][g]) if int(A["geom_type"][g]) == 7 else 0 for g in geoms}
+    admitted = set()
+    for i, a in enumerate(geoms):
+        for b in geoms[i + 1:]:
+            if link[a] == link[b]:
+                continue
+            if link[a] >= 0 and link[b] >= 0 and (S.parent_link(link[a]) == link[b] or S.parent_link(link[b]) == link[a]):
+                continue
+            if not ((A["geom_contype"][a] & A["geom_conaffinity"][b]) or (A["geom_contype"][b] & A["geom_conaffinity"][a])):
+                continue
+            if any(int(A["geom_type"][g]) == 7 and nvert[g] == 0 for g in (a, b)):
+                continue
+            if nvert[a] + nvert[b] > T["stage_verts"]:
+                continue
+            admitted.add((a, b))
+    gid = lambda i: T["geoms"][i]["geom_id"]  # noqa: E731
+    chk = [tuple(sorted((gid(p[0]), gid(p[1])))) for p in T["chk_pairs"]]
+    assert len(set(chk)) == len(chk) and T["chk_unchecked"] == 0 and len(chk) <= T["max_check_pairs"]
+    dropped = {tuple(sorted(p)) for p in T["never_touch"]} & admitted
+    assert set(chk) == admitted - dropped and admitted - set(chk) == dropped
+    if scene == "fr3_empty_world":
+        assert dropped == {(S.cm.name2id("geom", "fr3_link0_collision_0"), S.cm.name2id("geom", "fr3_link1_collision_0"))}
+    else:
+        assert dropped == set()
+    # geom[0] / geom[1] by type, then id; the callbacks' classes from the configurations' lists
+    for p in T["chk_pairs"]:
+        g0, g1, l0, l1, cls, joints = gid(p[0]), gid(p[1]), p[2], p[3], p[4], p[5]
+        assert (int(A["geom_type"][g0]), g0) < (int(A["geom_type"][g1]), g1)
+        assert (l0, l1) == (link[g0], link[g1])
+        want = 1 if (g0 in S.arm or g1 in S.arm) else 0
+        if not (g0 in S.fing and g1 in S.fing) and (g0 in S.grp or g1 in S.grp) and g1 not in S.ign:
+            want |= 2
+        assert cls == want, (g0, g1, cls, want)
+        r0, r1 = set(S.root_path(l0)), set(S.root_path(l1))
+        assert joints == sum(1 << j for j in r0 ^ r1), (g0, g1, joints)
+    key = lambda p: tuple(p)  # noqa: E731
+    assert sorted(map(key, T["pairs"])) == sorted(key(p) for p in T["chk_pairs"] if p[4] != 0)
+    assert T["ctab_npair"] == len(T["pairs"]) > 0 and T["chk_npair"] == len(T["chk_ent"]) == len(T["chk_pairs"]) and T["chk_ngeom"] == len(geoms)
+    body_pair = [(min(p[2], p[3]), max(p[2], p[3])) for p in T["chk_pairs"]]
+    assert body_pair == sorted(body_pair)
+    for p, e in zip(T["chk_pairs"], T["chk_ent"]):
+        assert e[:2] == p[:2]
+        common = [k for k in S.root_path(p[2]) if k in S.root_path(p[3])]
+        assert e[2] == (common[0] + 1 if common else 0), (p, e)
+
+
+@pytest.mark.parametrize("scene", SCENES)
+def test_one_box_rule(built, scenes, scene):
+    """The helper's box of a geom in its link's frame contains every hull vertex, box corner and capsule extreme, and it is the box the
+    check's per-geom tables carry (CheckTable::gh, CheckGeom::c / rot)."""
+    T, S = built[scene], scenes[scene]
+    n = 0
+    for g in T["geoms"]:
+        c, h, rot = np.array(g["box_c"]), np.array(g["box_h"]), np.array(g["box_rot"]).reshape(3, 3)
+        assert g["gh"] == g["box_h"] and g["chk_c"] == g["box_c"] and g["chk_rot"] == g["box_rot"] == g["rot"]
+        assert g["glink"] == g["link"] and g["gtype"] == g["type"]
+        pts = S.geom_points(g["geom_id"])
+        if len(pts) == 0:
+            continue  # a hull whose mesh is not in the checkout
+        in_link = np.array(g["pos"]) + pts @ np.array(g["rot"]).reshape(3, 3).T
+        local = (in_link - c) @ rot
+        assert (np.abs(local) <= h + 1e-12).all(), (scene, g["geom_id"], (np.abs(local) - h).max())
+        assert (np.abs(local).max(axis=0) >= h - 1e-12).all()  # ... and it is the tightest such box along the geom's axes
+        n += 1
+    assert n >= 19

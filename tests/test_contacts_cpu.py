@@ -487,7 +487,7 @@ def test_pad_against_pad_contacts_of_the_two_fingers():
 
 
 def test_link0_and_link1_never_touch_over_joint_1s_range():
-    """Round 5: the HIP side drops geom pairs that cannot touch across the arm's first hinge (csrc/rcs_hip.hip:
+    """Round 5: the HIP side drops geom pairs that cannot touch across the arm's first hinge (csrc/model.cpp:
     never_touch_across_first_hinge -- a geom welded to the world against a geom of link 1: a rotation about joint 1 leaves every
     point's coordinate along the axis alone, and the two hulls' extents along it do not overlap).  MuJoCo's filters admit the pair
     (the parent is static), and the oracle tests it in every substep: over joint 1's whole range, every other joint swept too, it
