@@ -587,6 +587,69 @@ int rcsh_debug_dump_model(rcsh_sim* sim, void* buf, size_t cap, size_t* size);
 int rcsh_prof_enable(rcsh_sim* sim, int32_t enable);
 int rcsh_prof_read(rcsh_sim* sim, double* total_ms, int64_t* launches);
 
+/* ---- autoreset: finished episodes are reset on the device inside the fused env step (Gymnasium's VectorEnv autoreset, SAME_STEP
+ * mode), so that a resident rollout never returns to the host because episodes end.  When enabled, rcsh_env_step_dev,
+ * rcsh_env_step_task_dev and their host forms enqueue, behind the stepping launch (and behind a truncating guard's mark), one launch
+ * that decides per environment (csrc/episode_team.h: k_episode_end)
+ *   time_limit = max_episode_steps > 0 && elapsed >= max_episode_steps   (Gymnasium's TimeLimit; elapsed counts this step)
+ *   terminated = the pick task is configured && the step's success        (task row, element 8)
+ *   truncated  = info row byte 4 || time_limit,    done = terminated || truncated
+ * writes time_limit into byte 4 of the caller's info row, adds the step's reward (task row, element 7; 0 without the pick task) to the
+ * environment's running return in fp64, and for a done environment copies the step's observation, info row, gripper width and task
+ * row into the record's final_*, writes the finished episode's return and length, zeroes both counters and counts the episode.  Then
+ * the masked reset launch -- rcsh_env_reset_dev's, or with draw_box rcsh_env_reset_task_dev's with the poses drawn below -- runs with
+ * `done` as its mask: it writes the new episode's first observation and gripper width into the rows of the done environments in the
+ * CALLER's obs / gripper_width buffers, and its info rows into the record's reset_info.  The caller's info, substeps and task rows
+ * are still the terminal step's after the call (a loop that reads info[:, 4] or task[:, 7:9] gets the terminal reward).  The reset
+ * launch is enqueued whether or not anyone is done -- the host does not know --; a workgroup whose environments all sit out leaves
+ * after its prologue.  A null obs / info / gripper_width (/ task, with the pick task) pointer of a _dev step stands for the library's
+ * own staging slice.
+ * Cube placement (draw_box) is counter-based -- an environment's draws depend neither on the batch size, nor on which other
+ * environments finish, nor on how the batch is sharded --: Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter
+ * (env_offset + e, k & 0xffffffff, k >> 32, j) with k the autoresets environment e has had before this one; j = 0 gives u0 (words
+ * 0, 1) and u1 (words 2, 3), j = 1 gives u2 (words 0, 1); a uniform in [0, 1) from words (a, b) is ((a << 32 | b) >> 11) * 2^-53.
+ * With p = box_pose (x y z qw qx qy qz): x = include_position ? (p[0] + u0 * 0.2) - 0.1 : p[0], y likewise from u1, z = p[2],
+ * qw = include_rotation ? 2 * u2 - rotation_minus : p[3], qx qy qz = p[4..6], every operation rounded on its own.  RandomCubePos:
+ * p = (iso_x, iso_y, 0.0144, 0, 0, 0, 1), rotation_minus = 1; RandomObjectPos: p = the initial pose, rotation_minus = its w.
+ * With autoreset configured, rcsh_env_reset* (masked or not) also zeroes elapsed and running_return of the environments it resets
+ * (episodes stays); rcsh_env_configure_autoreset zeroes every counter.  The counters are NOT part of rcsh_sim_get_state /
+ * rcsh_sim_set_state: the blob's size and layout are what they were (as with the rate-driven cameras' clocks, a restored handle
+ * keeps the counters it has).
+ * RCSH_ERR_ARG: null description, negative max_episode_steps or env_offset, env_offset + N > 2^32, a non-finite pose (checked before
+ * the handle is looked at); RCSH_ERR_STATE: before rcsh_env_configure, draw_box without rcsh_env_configure_pick_task, while a render
+ * schedule is set (rate-driven cameras under autoreset are not built; rcsh_sim_set_render_schedule in turn refuses while autoreset
+ * is enabled), and for the record before any step under autoreset.  A refused call changes nothing. */
+typedef struct rcsh_autoreset_desc {
+  int32_t enabled;            /* 0: steps run as before (the configuration and the counters are kept) */
+  int32_t max_episode_steps;  /* 0: no time limit */
+  int32_t draw_box;           /* 1: a done environment's free body is placed by the rule above (needs rcsh_env_configure_pick_task) */
+  int32_t include_position, include_rotation;
+  int64_t env_offset;         /* this handle's first environment in a sharded batch */
+  uint64_t seed;
+  double box_pose[7];
+  double rotation_minus;
+} rcsh_autoreset_desc;
+int rcsh_env_configure_autoreset(rcsh_sim* sim, const rcsh_autoreset_desc* autoreset);
+/* The record of the most recent step under autoreset: device pointers, valid for the handle's life, rewritten by every such step. */
+typedef struct rcsh_autoreset_record {
+  const uint8_t *done, *terminated, *truncated, *time_limit;          /* [N] */
+  const double* final_obs; const uint8_t* final_info; const double *final_gripper_width, *final_task; /* rows of done environments (others: stale) */
+  const double* episode_return; const int32_t* episode_length;        /* of the episode that just ended, where done */
+  const int64_t* episodes; const int32_t* elapsed; const double* running_return;
+  const uint8_t* reset_info; const double* reset_box_qpos;            /* [N][8], [N][7]: rows of done environments */
+} rcsh_autoreset_record;
+int rcsh_env_autoreset_record_dev(rcsh_sim* sim, rcsh_autoreset_record* out);
+/* The same record copied to host arrays, any of which may be NULL (after rcsh_env_step / rcsh_env_step_task the verdict bytes, the
+ * returns and the lengths come from the copy that step fetched with its own outputs: no further wait). */
+int rcsh_env_autoreset_last(rcsh_sim* sim, uint8_t* done, uint8_t* terminated, uint8_t* truncated, uint8_t* time_limit, double* final_obs,
+                            uint8_t* final_info, double* final_gripper_width, double* final_task, double* episode_return,
+                            int32_t* episode_length, int64_t* episodes, int32_t* elapsed, double* running_return, uint8_t* reset_info,
+                            double* reset_box_qpos);
+/* Host only (no handle, no device): the pose the device draws for environment `env` of a handle with this description at its
+ * autoreset number `episode`.  RCSH_ERR_ARG for a description rcsh_env_configure_autoreset would refuse on its own, a negative env or
+ * episode, env_offset + env >= 2^32, a null output. */
+int rcsh_autoreset_draw(const rcsh_autoreset_desc* autoreset, int64_t env, int64_t episode, double qpos7[7]);
+
 #ifdef __cplusplus
 }
 #endif

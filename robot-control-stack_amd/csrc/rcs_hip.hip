@@ -18,6 +18,7 @@
 #include "render.h"
 #include "query_team.h"
 #include "guard_team.h"
+#include "episode_team.h"
 
 using namespace rcsh;
 
@@ -41,6 +42,7 @@ constexpr int kBlock = 64;     // accessor kernels
 constexpr int kProfRing = 4096;
 
 }  // namespace
+int rcsh::episode_fail(int code, const char* msg) { return fail(code, msg); }  // (csrc/episode_host.cpp reports through rcsh_last_error)
 
 struct CopyCarrier;
 // a buffer that grows on demand (grow_device / grow_pinned)
@@ -104,6 +106,14 @@ struct rcsh_sim {
   bool guard_stepped = false;        // a guarded step has filled the first record
   char* h_guard = nullptr;           // page-locked copy of that record: rcsh_env_step fetches it with its own outputs (one synchronisation)
   bool guard_host_valid = false;     // ... and it is the last guarded step's
+  // autoreset (episode_team.h; rcsh_env_configure_autoreset): the description, the record every step under autoreset rewrites
+  // (EpisodeLayout), and a page-locked copy of the record's front (verdict bytes, returns, lengths) that the host forms of env.step
+  // fetch with their own outputs
+  struct AutoresetCfg { bool configured = false, enabled = false; rcsh_autoreset_desc desc{}; } autoreset;
+  void* d_episode = nullptr;
+  char* h_episode = nullptr;
+  bool episode_stepped = false;      // a step under autoreset has filled the record
+  bool episode_host_valid = false;   // ... and h_episode is that step's
   // per-environment escalation (sim_kernels.h: RunOp::esc_role): a step is the lean launch over the environments not in contact plus
   // the contact-resolving launch over the others
   bool esc_mode = false;
@@ -617,6 +627,27 @@ GuardLayout guard_layout(const rcsh_sim* s) {
   return G;
 }
 
+// the autoreset's record (rcsh_sim::d_episode; offsets in bytes, every slice 8-byte aligned).  The front -- up to host_bytes -- is what
+// a host form of env.step brings along: [episode_return | episode_length | done | terminated | truncated | time_limit]
+struct EpisodeLayout {
+  size_t episode_return, episode_length, done, terminated, truncated, time_limit, host_bytes;
+  size_t final_obs, final_info, final_gw, final_task, episodes, elapsed, running_return, reset_info, reset_box_qpos, bytes;
+};
+EpisodeLayout episode_layout(const rcsh_sim* s) {
+  const size_t n = (size_t)s->n;
+  EpisodeLayout E{};
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += align8(bytes); return at; };
+  E.episode_return = take(8 * n); E.episode_length = take(4 * n);
+  E.done = take(n); E.terminated = take(n); E.truncated = take(n); E.time_limit = take(n);
+  E.host_bytes = o;
+  E.final_obs = take(8 * n * (size_t)(kObsBase + s->narm)); E.final_info = take(n * kInfoBytes); E.final_gw = take(8 * n);
+  E.final_task = take(8 * n * kTaskWidth); E.episodes = take(8 * n); E.elapsed = take(4 * n); E.running_return = take(8 * n);
+  E.reset_info = take(n * kInfoBytes); E.reset_box_qpos = take(8 * n * kPoseWidth);
+  E.bytes = o;
+  return E;
+}
+
 // the page-locked buffer (laid out by rcsh_sim::pin), allocated at its first use
 int pin_ready(rcsh_sim* s, char*& h) {
   int rc = grow_pinned(s, s->h_pin, s->pin.total);
@@ -630,9 +661,10 @@ int pin_upload(rcsh_sim* s, void* dev, char* pinned, const void* src, size_t byt
   return RCSH_OK;
 }
 // How the env layer's host forms end: the requested outputs go from their slices to page-locked memory -- with the last guarded step's
-// record, if asked: rcsh_env_guard_last then needs no wait of its own --, ONE wait, and out to the caller's arrays.
+// record and the front of the autoreset's, if asked: rcsh_env_guard_last / rcsh_env_autoreset_last then need no wait of their own --,
+// ONE wait, and out to the caller's arrays.
 struct EnvOut { double* obs; uint8_t* info; double* gw; int32_t* substeps; double* task; };
-int fetch_env_outputs(rcsh_sim* s, const EnvOut& out, bool guard_record_too) {
+int fetch_env_outputs(rcsh_sim* s, const EnvOut& out, bool guard_record_too, bool episode_record_too = false) {
   const PinLayout& L = s->pin;
   char* h = nullptr;
   int rc = pin_ready(s, h);
@@ -646,6 +678,7 @@ int fetch_env_outputs(rcsh_sim* s, const EnvOut& out, bool guard_record_too) {
   for (const auto& p : pieces)
     if (p.dst) HIP_TRY(hipMemcpyAsync(h + p.at, p.src, p.bytes, hipMemcpyDeviceToHost, s->stream));
   if (guard_record_too) HIP_TRY(hipMemcpyAsync(s->h_guard, s->d_guard, guard_layout(s).host_bytes, hipMemcpyDeviceToHost, s->stream));
+  if (episode_record_too) HIP_TRY(hipMemcpyAsync(s->h_episode, s->d_episode, episode_layout(s).host_bytes, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   for (const auto& p : pieces)
     if (p.dst) std::memcpy(p.dst, h + p.at, p.bytes);
@@ -771,6 +804,8 @@ void rcsh_sim_destroy(rcsh_sim* s) {
   hipFree(s->d_query.p);
   hipFree(s->d_guard);
   if (s->h_guard) hipHostFree(s->h_guard);
+  hipFree(s->d_episode);
+  if (s->h_episode) hipHostFree(s->h_episode);
   hipFree(s->d_esc); hipFree(s->d_esc_ctr); hipFree(s->d_snap); hipFree(s->d_snap_flags); hipFree(s->d_snap_conv);
   hipFree(s->rend.last); hipFree(s->rend.snap); hipFree(s->rend.count);
   hipFree(s->d_boxtask); hipFree(s->d_rshapes); hipFree(s->d_rplanes); hipFree(s->d_rcolours); hipFree(s->d_frames); hipFree(s->d_wframes); hipFree(s->d_image.p);
@@ -1658,16 +1693,150 @@ int rcsh_env_action_width(const rcsh_sim* s) {
   return action_width(s->env.mode, s->narm);
 }
 
-int rcsh_env_reset_dev(rcsh_sim* s, const uint8_t* mask_dev, double* obs_dev, uint8_t* info_dev, double* gw_dev) {
+// ---- autoreset (csrc/episode_team.h)
+namespace {
+struct EpisodeRecord {
+  uint8_t *done, *terminated, *truncated, *time_limit;
+  double* final_obs; uint8_t* final_info; double *final_gw, *final_task;
+  double* episode_return; int32_t* episode_length;
+  int64_t* episodes; int32_t* elapsed; double* running_return;
+  uint8_t* reset_info; double* reset_box_qpos;
+};
+EpisodeRecord episode_record(const rcsh_sim* s) {
+  const EpisodeLayout E = episode_layout(s);
+  char* d = static_cast<char*>(s->d_episode);
+  auto at = [&](size_t o, auto* type) { return reinterpret_cast<decltype(type)>(d + o); };
+  EpisodeRecord r{};
+  r.done = at(E.done, r.done); r.terminated = at(E.terminated, r.terminated); r.truncated = at(E.truncated, r.truncated);
+  r.time_limit = at(E.time_limit, r.time_limit);
+  r.final_obs = at(E.final_obs, r.final_obs); r.final_info = at(E.final_info, r.final_info); r.final_gw = at(E.final_gw, r.final_gw);
+  r.final_task = at(E.final_task, r.final_task);
+  r.episode_return = at(E.episode_return, r.episode_return); r.episode_length = at(E.episode_length, r.episode_length);
+  r.episodes = at(E.episodes, r.episodes); r.elapsed = at(E.elapsed, r.elapsed); r.running_return = at(E.running_return, r.running_return);
+  r.reset_info = at(E.reset_info, r.reset_info); r.reset_box_qpos = at(E.reset_box_qpos, r.reset_box_qpos);
+  return r;
+}
+// an explicit env reset begins the episodes of the environments it resets again
+int episode_clear(rcsh_sim* s, const uint8_t* mask_dev) {
+  if (!s->autoreset.configured) return RCSH_OK;
+  const EpisodeRecord r = episode_record(s);
+  hipLaunchKernelGGL(k_episode_clear, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, mask_dev, r.elapsed, r.running_return, s->n);
+  HIP_TRY(hipGetLastError());
+  return RCSH_OK;
+}
+// What follows the stepping launch of a step under autoreset: k_episode_end over the step's outputs, then the masked reset launch
+// (rcsh_env_reset_dev's, or rcsh_env_reset_task_dev's with the poses just drawn) with `done` as its mask -- always enqueued, the host
+// does not know who is done --, writing the new episodes' first observation into the step's own obs / gripper_width rows.
+int episode_end(rcsh_sim* s, double* obs, uint8_t* info, double* gw, const double* task) {
+  const EpisodeRecord r = episode_record(s);
+  const rcsh_autoreset_desc& a = s->autoreset.desc;
+  EpisodeArgs A{};
+  A.n = s->n; A.obs_w = kObsBase + s->narm; A.max_steps = a.max_episode_steps; A.draw_box = a.draw_box != 0;
+  A.envs_per_block = kEpisodeBlock / episode_row_items(A.obs_w);
+  if (A.envs_per_block < 1) return fail(RCSH_ERR_MODEL, "an environment's rows do not fit one workgroup of k_episode_end");
+  A.obs = obs; A.info = info; A.gw = gw; A.task = s->task.pick_cube ? task : nullptr;
+  A.done = r.done; A.terminated = r.terminated; A.truncated = r.truncated; A.time_limit = r.time_limit;
+  A.final_obs = r.final_obs; A.final_info = r.final_info; A.final_gw = r.final_gw; A.final_task = r.final_task;
+  A.episode_return = r.episode_return; A.episode_length = r.episode_length;
+  A.episodes = r.episodes; A.elapsed = r.elapsed; A.running_return = r.running_return;
+  A.reset_box_qpos = r.reset_box_qpos;
+  A.draw = episode_draw_of(a);
+  hipLaunchKernelGGL(k_episode_end, dim3((s->n + A.envs_per_block - 1) / A.envs_per_block), dim3(kEpisodeBlock), 0, s->stream, A);
+  HIP_TRY(hipGetLastError());
+  RunOp op{};
+  op.do_reset = 1;
+  op.nsteps = 1;
+  op.write_obs = 1;
+  op.mask = r.done;
+  op.box_qpos = A.draw_box ? r.reset_box_qpos : nullptr;
+  op.obs = obs; op.info = r.reset_info; op.gripper_width = gw;
+  int rc = launch_run(s, op, false);
+  if (rc) return rc;
+  s->episode_stepped = true;
+  s->episode_host_valid = false;
+  return RCSH_OK;
+}
+}  // namespace
+
+int rcsh_env_configure_autoreset(rcsh_sim* s, const rcsh_autoreset_desc* a) {
+  if (const char* why = autoreset_desc_error(a, 0)) return fail(RCSH_ERR_ARG, why);  // (what needs no handle comes first)
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (const char* why = autoreset_desc_error(a, s->n)) return fail(RCSH_ERR_ARG, why);
   if (!s->env_configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure first");
+  if (a->draw_box && !s->task.pick_cube) return fail(RCSH_ERR_STATE, "draw_box places the pick task's cube: call rcsh_env_configure_pick_task first");
+  if (s->rend.ncam > 0)
+    return fail(RCSH_ERR_STATE, "a render schedule is set: rate-driven cameras under autoreset are not built (remove it with rcsh_sim_set_render_schedule(ncam = 0) first)");
+  const EpisodeLayout E = episode_layout(s);
+  if (!s->d_episode) HIP_TRY(hipMalloc(&s->d_episode, E.bytes));
+  if (!s->h_episode) { void* p = nullptr; HIP_TRY(hipHostMalloc(&p, E.host_bytes, hipHostMallocDefault)); s->h_episode = (char*)p; }
+  HIP_TRY(hipMemsetAsync(s->d_episode, 0, E.bytes, s->stream));  // every counter begins again
+  s->autoreset.configured = true;
+  s->autoreset.enabled = a->enabled != 0;
+  s->autoreset.desc = *a;
+  s->episode_stepped = false;
+  s->episode_host_valid = false;
+  return RCSH_OK;
+}
+
+int rcsh_env_autoreset_record_dev(rcsh_sim* s, rcsh_autoreset_record* out) {
+  REQUIRE_SIM(s);
+  if (!s->autoreset.configured || !s->episode_stepped) return fail(RCSH_ERR_STATE, "no step under autoreset has run");
+  if (!out) return fail(RCSH_ERR_ARG, "null record");
+  const EpisodeRecord r = episode_record(s);
+  out->done = r.done; out->terminated = r.terminated; out->truncated = r.truncated; out->time_limit = r.time_limit;
+  out->final_obs = r.final_obs; out->final_info = r.final_info; out->final_gripper_width = r.final_gw; out->final_task = r.final_task;
+  out->episode_return = r.episode_return; out->episode_length = r.episode_length;
+  out->episodes = r.episodes; out->elapsed = r.elapsed; out->running_return = r.running_return;
+  out->reset_info = r.reset_info; out->reset_box_qpos = r.reset_box_qpos;
+  return RCSH_OK;
+}
+
+int rcsh_env_autoreset_last(rcsh_sim* s, uint8_t* done, uint8_t* terminated, uint8_t* truncated, uint8_t* time_limit, double* final_obs,
+                            uint8_t* final_info, double* final_gripper_width, double* final_task, double* episode_return,
+                            int32_t* episode_length, int64_t* episodes, int32_t* elapsed, double* running_return, uint8_t* reset_info,
+                            double* reset_box_qpos) {
+  REQUIRE_SIM(s);
+  if (!s->autoreset.configured || !s->episode_stepped) return fail(RCSH_ERR_STATE, "no step under autoreset has run");
+  const size_t n = (size_t)s->n;
+  const EpisodeLayout E = episode_layout(s);
+  const char* d = static_cast<const char*>(s->d_episode);
+  const struct { void* dst; size_t at, bytes; bool front; } pieces[] = {
+      {episode_return, E.episode_return, 8 * n, true}, {episode_length, E.episode_length, 4 * n, true},
+      {done, E.done, n, true}, {terminated, E.terminated, n, true}, {truncated, E.truncated, n, true}, {time_limit, E.time_limit, n, true},
+      {final_obs, E.final_obs, 8 * n * (size_t)(kObsBase + s->narm), false}, {final_info, E.final_info, n * kInfoBytes, false},
+      {final_gripper_width, E.final_gw, 8 * n, false}, {final_task, E.final_task, 8 * n * kTaskWidth, false},
+      {episodes, E.episodes, 8 * n, false}, {elapsed, E.elapsed, 4 * n, false}, {running_return, E.running_return, 8 * n, false},
+      {reset_info, E.reset_info, n * kInfoBytes, false}, {reset_box_qpos, E.reset_box_qpos, 8 * n * kPoseWidth, false}};
+  bool wait = false;
+  for (const auto& p : pieces) {
+    if (!p.dst) continue;
+    if (p.front && s->episode_host_valid) { std::memcpy(p.dst, s->h_episode + p.at, p.bytes); continue; }  // (rcsh_env_step brought it along)
+    HIP_TRY(hipMemcpyAsync(p.dst, d + p.at, p.bytes, hipMemcpyDeviceToHost, s->stream));
+    wait = true;
+  }
+  if (wait) HIP_TRY(hipStreamSynchronize(s->stream));
+  return RCSH_OK;
+}
+
+namespace {
+// env.reset's launch: with the box pose of the pick-up task's reset, or without
+int env_reset_launch(rcsh_sim* s, const uint8_t* mask_dev, const double* box_qpos_dev, double* obs_dev, uint8_t* info_dev, double* gw_dev) {
   RunOp op{};
   op.do_reset = 1;
   op.nsteps = 1;
   op.write_obs = obs_dev != nullptr;
   op.mask = mask_dev;
+  op.box_qpos = box_qpos_dev;
   op.obs = obs_dev; op.info = info_dev; op.gripper_width = gw_dev;
-  return launch_run(s, op, false);
+  int rc = launch_run(s, op, false);
+  return rc ? rc : episode_clear(s, mask_dev);
+}
+}  // namespace
+
+int rcsh_env_reset_dev(rcsh_sim* s, const uint8_t* mask_dev, double* obs_dev, uint8_t* info_dev, double* gw_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (!s->env_configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure first");
+  return env_reset_launch(s, mask_dev, nullptr, obs_dev, info_dev, gw_dev);
 }
 
 // ---- the collision guard (csrc/guard_team.h)
@@ -1814,6 +1983,15 @@ int rcsh_env_step_dev(rcsh_sim* s, const double* action_dev, const float* grippe
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!s->env_configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure first");
   if (!action_dev) return fail(RCSH_ERR_ARG, "null action");
+  double* task_dev = s->pending_task;
+  const bool autoreset = s->autoreset.enabled;
+  if (autoreset) {  // (k_episode_end reads the step's outputs: an output the caller does not ask for goes to the staging slice)
+    const Staging& st = s->stage;
+    if (!obs_dev) obs_dev = st.obs;
+    if (!info_dev) info_dev = st.info;
+    if (!gw_dev) gw_dev = st.grip_width;
+    if (!task_dev && s->task.pick_cube) task_dev = st.box_task;
+  }
   RunOp op{};
   op.apply_action = 1;
   const bool guarded = s->guard.enabled && s->env.mode == RCSH_MODE_JOINTS;  // (rcsh_env_configure refuses a Cartesian mode under a guard)
@@ -1841,7 +2019,7 @@ int rcsh_env_step_dev(rcsh_sim* s, const double* action_dev, const float* grippe
   op.write_obs = obs_dev != nullptr;
   op.action = action_dev; op.gripper = gripper_dev;
   op.obs = obs_dev; op.info = info_dev; op.gripper_width = gw_dev; op.substeps = substeps_dev;
-  op.task = s->pending_task;
+  op.task = task_dev;
   int rc = launch_run(s, op, true);
   if (rc) return rc;
   if (guarded) { s->guard_stepped = true; s->guard_host_valid = false; }
@@ -1849,6 +2027,7 @@ int rcsh_env_step_dev(rcsh_sim* s, const double* action_dev, const float* grippe
     hipLaunchKernelGGL(k_guard_truncate, dim3((s->n + 63) / 64), dim3(64), 0, s->stream, info_dev, guard_record(s, 0).blocked, s->n);
     HIP_TRY(hipGetLastError());
   }
+  if (autoreset) return episode_end(s, obs_dev, info_dev, gw_dev, task_dev);
   return RCSH_OK;
 }
 
@@ -1870,14 +2049,7 @@ int rcsh_env_reset_task_dev(rcsh_sim* s, const uint8_t* mask_dev, const double* 
   if (!s->env_configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure first");
   if (!s->task.pick_cube) return fail(RCSH_ERR_STATE, "call rcsh_env_configure_pick_task first");
   if (!box_qpos_dev) return fail(RCSH_ERR_ARG, "null box pose");
-  RunOp op{};
-  op.do_reset = 1;
-  op.nsteps = 1;
-  op.write_obs = obs_dev != nullptr;
-  op.mask = mask_dev;
-  op.box_qpos = box_qpos_dev;
-  op.obs = obs_dev; op.info = info_dev; op.gripper_width = gw_dev;
-  return launch_run(s, op, false);
+  return env_reset_launch(s, mask_dev, box_qpos_dev, obs_dev, info_dev, gw_dev);
 }
 
 int rcsh_env_step_task_dev(rcsh_sim* s, const double* action_dev, const float* gripper_dev, double* obs_dev, uint8_t* info_dev,
@@ -1927,8 +2099,10 @@ int env_step_host(rcsh_sim* s, const double* action, const float* gripper, const
   s->pending_task = nullptr;
   if (rc) return rc;
   const bool guard_record_too = s->guard.enabled && s->guard_stepped && s->h_guard;
-  if ((rc = fetch_env_outputs(s, out, guard_record_too))) return rc;
+  const bool episode_record_too = s->autoreset.enabled && s->episode_stepped && s->h_episode;
+  if ((rc = fetch_env_outputs(s, out, guard_record_too, episode_record_too))) return rc;
   s->guard_host_valid = guard_record_too;
+  s->episode_host_valid = episode_record_too;
   return RCSH_OK;
 }
 }  // namespace
@@ -2105,6 +2279,8 @@ int rcsh_sim_set_render_schedule(rcsh_sim* s, const int32_t* cam_ids, const doub
   if (!s->d_frames) return fail(RCSH_ERR_STATE, "no render scene: call rcsh_sim_set_render_scene first");
   if (ncam < 0 || ncam > kMaxRateCams) return fail(RCSH_ERR_ARG, "render schedule: at most 4 cameras with a frame rate");
   if (ncam > 0 && (!cam_ids || !seconds_between_calls || capacity < 1 || capacity > 256)) return fail(RCSH_ERR_ARG, "render schedule: bad arguments");
+  if (ncam > 0 && s->autoreset.enabled)
+    return fail(RCSH_ERR_STATE, "autoreset is enabled: rate-driven cameras under autoreset are not built (disable it with rcsh_env_configure_autoreset first)");
   for (int c = 0; c < ncam; ++c) {
     if (cam_ids[c] < 0 || cam_ids[c] >= (int)s->cams.size()) return fail(RCSH_ERR_ARG, "render schedule: unknown camera id");
     if (!(seconds_between_calls[c] > 0)) return fail(RCSH_ERR_ARG, "render schedule: the period must be positive");

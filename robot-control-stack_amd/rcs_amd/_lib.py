@@ -160,6 +160,19 @@ class GuardDesc(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("kinds", C.c_int32), ("resolution", C.c_double), ("block_undecided", C.c_int32), ("truncate", C.c_int32)]
 
 
+class AutoresetDesc(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("max_episode_steps", C.c_int32), ("draw_box", C.c_int32), ("include_position", C.c_int32),
+                ("include_rotation", C.c_int32), ("env_offset", C.c_int64), ("seed", C.c_uint64), ("box_pose", C.c_double * 7),
+                ("rotation_minus", C.c_double)]
+
+
+class AutoresetRecord(C.Structure):
+    """Device pointers of the autoreset's record (rcsh_env_autoreset_record_dev)."""
+    _fields_ = [(name, C.c_void_p) for name in (
+        "done", "terminated", "truncated", "time_limit", "final_obs", "final_info", "final_gripper_width", "final_task",
+        "episode_return", "episode_length", "episodes", "elapsed", "running_return", "reset_info", "reset_box_qpos")]
+
+
 # every symbol include/rcs_hip.h declares; load() fails if one is missing
 EXPORTS = (
     "rcsh_last_error", "rcsh_abi_version", "rcsh_device_count", "rcsh_sim_create", "rcsh_sim_destroy",
@@ -190,6 +203,7 @@ EXPORTS = (
     "rcsh_sim_contact_overflow",
     "rcsh_collision_query", "rcsh_collision_query_dev", "rcsh_motion_query", "rcsh_motion_query_dev",
     "rcsh_env_configure_guard", "rcsh_env_guard_peek", "rcsh_env_guard_peek_dev", "rcsh_env_guard_last", "rcsh_env_guard_last_dev",
+    "rcsh_env_configure_autoreset", "rcsh_env_autoreset_record_dev", "rcsh_env_autoreset_last", "rcsh_autoreset_draw",
 )
 
 _lib = None
@@ -276,6 +290,10 @@ def load() -> C.CDLL:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rcsh_env_guard_last.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rcsh_env_guard_last_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.rcsh_env_configure_autoreset.argtypes = [C.c_void_p, C.POINTER(AutoresetDesc)]
+    L.rcsh_env_autoreset_record_dev.argtypes = [C.c_void_p, C.POINTER(AutoresetRecord)]
+    L.rcsh_env_autoreset_last.argtypes = [C.c_void_p] + [C.c_void_p] * 15
+    L.rcsh_autoreset_draw.argtypes = [C.POINTER(AutoresetDesc), C.c_int64, C.c_int64, _F64P]
     _lib = L
     return L
 

@@ -38,6 +38,13 @@ class VecSimEnv:
     the device, whether the straight joint-space motion from where each arm is to where its action sends it is proven free of
     contact (csrc/guard_team.h).  A blocked environment is commanded to stay where it is and -- with ``truncate_on_collision`` -- is
     reported ``terminated`` and ``truncated``; ``info`` gains ``guard_blocked``, ``guard_result`` and ``guard_t_contact``.
+
+    With autoreset (:meth:`configure_autoreset`; Gymnasium's ``VectorEnv`` autoreset in its SAME_STEP mode) an environment whose episode
+    ends -- ``terminated``, ``truncated``, or a time limit -- is reset on the device inside the same step: the returned ``obs`` rows of
+    those environments are the new episode's first observation, ``terminated`` / ``truncated`` / the reward are the terminal step's,
+    and ``info`` gains ``autoreset`` (done), ``TimeLimit.truncated``, ``episode`` (``{"r", "l"}``, valid where done) and ``final_obs``
+    (the observation dict of the terminal step in the done rows, zeros elsewhere).  A ``CameraSetWrapper``'s ``clear_buffer()`` is
+    global to the batch and is NOT called on an autoreset; rate-driven cameras cannot be combined with autoreset.
     """
 
     def __init__(self, simulation: sim.Sim, robot: sim.SimRobot, gripper: sim.SimGripper | None,
@@ -89,6 +96,8 @@ class VecSimEnv:
         self.on_unresolved_contact = "resolve"
         self.guard_enabled = False
         self.guard_truncates = True
+        self.autoreset_enabled = False
+        self.autoreset_desc: _lib.AutoresetDesc | None = None  # what the last configure_autoreset passed down (autoreset_draw reads it)
 
     # ---- collision guard (reference python/rcs/envs/sim.py:156-287: CollisionGuard between RelativeActionSpace and RobotEnv.step)
     def default_guard_kinds(self) -> int:
@@ -159,6 +168,93 @@ class VecSimEnv:
         i["guard_result"] = result
         i["guard_t_contact"] = tc
         return blocked if self.guard_truncates else None
+
+    # ---- autoreset (csrc/episode_team.h: finished episodes are reset inside the fused step)
+    def _autoreset_desc(self, enabled, max_episode_steps, seed, env_offset) -> _lib.AutoresetDesc:
+        d = _lib.AutoresetDesc()
+        d.enabled = int(bool(enabled))
+        d.max_episode_steps = 0 if max_episode_steps is None else int(max_episode_steps)
+        d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        d.env_offset = int(env_offset)
+        return d
+
+    def _apply_autoreset(self, d: _lib.AutoresetDesc) -> None:
+        _lib.check(self._L.rcsh_env_configure_autoreset(self.sim._h, C.byref(d)))
+        self.autoreset_enabled = bool(d.enabled)
+        self.autoreset_desc = d
+
+    def configure_autoreset(self, enabled: bool = True, max_episode_steps: int | None = None, seed: int = 0, env_offset: int = 0) -> None:
+        """Reset finished episodes on the device inside ``step`` / ``step_dev`` (see the class docstring).
+
+        ``max_episode_steps``: Gymnasium's ``TimeLimit`` (an episode is truncated by the step that brings its length to the limit;
+        ``None``: no limit).  ``seed`` / ``env_offset`` only matter where the new episode draws something (:class:`VecPickCubeEnv`):
+        ``env_offset`` is this env's first environment in a batch sharded over several Sims.  Every call zeroes the episode counters;
+        ``enabled=False`` makes the steps run as if autoreset had never been configured.  An explicit :meth:`reset` also begins the
+        episodes of the environments it resets again.  Not with rate-driven cameras (RuntimeError)."""
+        self._apply_autoreset(self._autoreset_desc(enabled, max_episode_steps, seed, env_offset))
+
+    def autoreset_draw(self, env: int, episode: int) -> np.ndarray:
+        """The cube pose the device draws for environment ``env`` at its ``episode``-th autoreset (computed on the host)."""
+        if self.autoreset_desc is None:
+            raise RuntimeError("call configure_autoreset first")
+        q = np.zeros(7)
+        _lib.check(self._L.rcsh_autoreset_draw(C.byref(self.autoreset_desc), int(env), int(episode), q.ctypes.data_as(C.POINTER(C.c_double))))
+        return q
+
+    _AUTORESET_FIELDS = (("done", np.uint8, ()), ("terminated", np.uint8, ()), ("truncated", np.uint8, ()), ("time_limit", np.uint8, ()),
+                         ("final_obs", np.float64, ("obs",)), ("final_info", np.uint8, (8,)), ("final_gripper_width", np.float64, ()),
+                         ("final_task", np.float64, (9,)), ("episode_return", np.float64, ()), ("episode_length", np.int32, ()),
+                         ("episodes", np.int64, ()), ("elapsed", np.int32, ()), ("running_return", np.float64, ()),
+                         ("reset_info", np.uint8, (8,)), ("reset_box_qpos", np.float64, (7,)))
+
+    def autoreset_last(self, fields=None) -> dict[str, np.ndarray]:
+        """The record of the most recent step under autoreset as host arrays (``fields``: a subset of its names; default all).
+        ``final_*`` and ``reset_*`` rows are meaningful where ``done``."""
+        out: dict[str, np.ndarray] = {}
+        args = []
+        for name, dtype, shape in self._AUTORESET_FIELDS:
+            if fields is not None and name not in fields:
+                args.append(None)
+                continue
+            out[name] = np.zeros((self.n_envs, *[self.obs_width if k == "obs" else k for k in shape]), dtype=dtype)
+            args.append(_lib.ptr(out[name]))
+        _lib.check(self._L.rcsh_env_autoreset_last(self.sim._h, *args))
+        return out
+
+    def autoreset_last_dev(self) -> _lib.AutoresetRecord:
+        """Device pointers of the record (``.done``, ``.final_obs``, ``.episode_return``, ...: integers), for ``step_dev`` loops: valid
+        for the Sim's life, rewritten by every step under autoreset."""
+        r = _lib.AutoresetRecord()
+        _lib.check(self._L.rcsh_env_autoreset_record_dev(self.sim._h, C.byref(r)))
+        return r
+
+    def _obs_dict(self, obs) -> dict[str, Any]:
+        d = self.dof
+        o: dict[str, Any] = {"tquat": obs[:, 0:7].copy(), "joints": obs[:, 7 : 7 + d].copy(), "xyzrpy": obs[:, 7 + d : 13 + d].copy()}
+        if self.gripper is not None:
+            o["gripper"] = obs[:, 13 + d].copy()
+        return o
+
+    def _autoreset_info(self, i: dict[str, Any], extra=()) -> None:
+        """info of a step under autoreset.  The verdict bytes, returns and lengths came with the step's own outputs; the terminal
+        observations are fetched only when somebody is done."""
+        if not self.autoreset_enabled:
+            return
+        rec = self.autoreset_last(("done", "time_limit", "episode_return", "episode_length"))
+        done = rec["done"].astype(bool)
+        i["autoreset"] = done
+        i["TimeLimit.truncated"] = rec["time_limit"].astype(bool)
+        i["episode"] = {"r": np.where(done, rec["episode_return"], 0.0), "l": np.where(done, rec["episode_length"], 0).astype(np.int32)}
+        final = np.zeros((self.n_envs, self.obs_width))
+        more = self.autoreset_last(("final_obs", *extra)) if done.any() else {}
+        if done.any():
+            final[done] = more["final_obs"][done]
+        i["final_obs"] = self._obs_dict(final)
+        for name in extra:
+            a = np.zeros((self.n_envs, 7))
+            if done.any():
+                a[done] = more[name][done]
+            i[name] = a
 
     def _after_step(self, info) -> None:
         if self.on_unresolved_contact == "resolve" and not self.sim.resolve_robot_contacts and info[:, 7].any():
@@ -238,6 +334,7 @@ class VecSimEnv:
         if stop is not None:
             terminated |= stop
             truncated |= stop
+        self._autoreset_info(i)  # (info row byte 4 -- `truncated` -- carries the time limit already)
         return o, np.zeros(n), terminated, truncated, i
 
     # ---- device-pointer interface for resident rollouts (pointers are integers / c_void_p)
@@ -245,7 +342,9 @@ class VecSimEnv:
         _lib.check(self._L.rcsh_env_reset_dev(self.sim._h, C.c_void_p(mask_ptr), C.c_void_p(obs_ptr), C.c_void_p(info_ptr), C.c_void_p(gw_ptr)))
 
     def step_dev(self, action_ptr, gripper_ptr, obs_ptr, info_ptr=None, gw_ptr=None, substeps_ptr=None) -> None:
-        """One resident step.  A configured guard applies here too: its record is at :meth:`guard_last_dev` / :meth:`guard_last`."""
+        """One resident step.  A configured guard applies here too: its record is at :meth:`guard_last_dev` / :meth:`guard_last`.
+        So does autoreset: the rows of done environments in ``obs`` / ``gw`` are the new episode's, the rest of the story is at
+        :meth:`autoreset_last_dev` / :meth:`autoreset_last`."""
         _lib.check(self._L.rcsh_env_step_dev(self.sim._h, C.c_void_p(action_ptr), C.c_void_p(gripper_ptr), C.c_void_p(obs_ptr),
                                              C.c_void_p(info_ptr), C.c_void_p(gw_ptr), C.c_void_p(substeps_ptr)))
 
@@ -282,6 +381,28 @@ class VecPickCubeEnv(VecSimEnv):
         t.success_height = float(self.SUCCESS_HEIGHT)
         _lib.check(self._L.rcsh_env_configure_pick_task(self.sim._h, C.byref(t)))
         self.task_width = 9
+
+    def configure_autoreset(self, enabled: bool = True, max_episode_steps: int | None = None, seed: int = 0, env_offset: int = 0) -> None:
+        """:meth:`VecSimEnv.configure_autoreset` of the task env: ``success`` terminates, the reward is summed into ``info["episode"]
+        ["r"]``, and a done environment's cube is placed on the device by the rule :meth:`draw_box_qpos` follows -- RandomCubePos, or
+        RandomObjectPos with ``random_pos_args`` -- from a counter-based generator keyed by ``seed``: environment ``env_offset + e``'s
+        k-th autoreset draws the same pose whatever the batch size and whoever else finishes (:meth:`autoreset_draw`;
+        ``info["reset_box_qpos"]``).  An explicit :meth:`reset` keeps drawing from numpy's global generator."""
+        d = self._autoreset_desc(enabled, max_episode_steps, seed, env_offset)
+        d.draw_box = 1
+        if self.random_pos_args is not None:
+            t, q = self.init_object_pose.translation(), self.init_object_pose.rotation_q()  # xyzw
+            d.include_position = int(bool(self.random_pos_args.get("include_position", True)))
+            d.include_rotation = int(bool(self.random_pos_args.get("include_rotation", False)))
+            d.box_pose[:] = [float(t[0]), float(t[1]), float(t[2]), float(q[3]), float(q[0]), float(q[1]), float(q[2])]
+            d.rotation_minus = float(q[3])
+        else:
+            iso = self.robot.to_pose_in_world_coordinates(common.Pose(translation=self.ISO_CUBE, rpy_vector=np.zeros(3))).translation()
+            d.include_position = 1
+            d.include_rotation = int(bool(self.include_rotation))
+            d.box_pose[:] = [float(iso[0]), float(iso[1]), 0.0288 / 2, 0.0, 0.0, 0.0, 1.0]
+            d.rotation_minus = 1.0
+        self._apply_autoreset(d)
 
     def draw_box_qpos(self) -> np.ndarray:
         """RandomCubePos.reset's placement (sim.py:371-383) -- or RandomObjectPos.reset's (sim.py:331-354) -- for every
@@ -349,6 +470,7 @@ class VecPickCubeEnv(VecSimEnv):
         if stop is not None:
             terminated |= stop
             truncated |= stop
+        self._autoreset_info(i, extra=("reset_box_qpos",))
         return o, task[:, 7].copy(), terminated, truncated, i
 
     def step_task_dev(self, action_ptr, gripper_ptr, obs_ptr, info_ptr=None, gw_ptr=None, substeps_ptr=None, task_ptr=None) -> None:
