@@ -486,12 +486,17 @@ class Sim:
     # common.Kinematics (Pin) on the robot's chain
     def ik_inverse(self, pose: Pose, q0, tcp_offset: Pose | None = None):
         """Pin::inverse: (q[model.nq] or None, iterations)."""
+        ok, q, it = self.ik_inverse_last(pose, q0, tcp_offset)
+        return (q if ok else None), it
+
+    def ik_inverse_last(self, pose: Pose, q0, tcp_offset: Pose | None = None):
+        """Pin::inverse with the iterate it stopped at: (success, q[model.nq], iterations) -- on failure the iterate of the 1000th step."""
         q0 = np.ascontiguousarray(q0, dtype=np.float64)
         out = (D * MAXV)()
         it = I(0)
         off = (tcp_offset or Pose()).p
         ok = lib().orc_ik_inverse(C.byref(self.s.ik), C.byref(pose.p), (D * len(q0))(*q0), len(q0), C.byref(off), out, C.byref(it))
-        return (np.array(out[: self.model.njnt]) if ok else None), int(it.value)
+        return bool(ok), np.array(out[: self.model.njnt]), int(it.value)
 
     def ik_forward(self, q0, tcp_offset: Pose | None = None) -> Pose:
         q0 = np.ascontiguousarray(q0, dtype=np.float64)

@@ -410,7 +410,7 @@ static void ldlt6_solve(double A[6][6], double* x) {
   for (int i = 5; i >= 0; i--) for (int k = i + 1; k < 6; k++) x[i] -= L[k][i] * x[k];
 }
 
-/* Pin::inverse, Kinematics.cpp:28-68.  Returns 1 on success (q_out has model.nq entries). */
+/* Pin::inverse, Kinematics.cpp:28-68.  Returns 1 on success (q_out has model.nq entries: the solution, or the last iterate). */
 int orc_ik_inverse(const orc_ik* ik, const orc_pose* pose, const double* q0, int nq0, const orc_pose* tcp_offset,
                    double* q_out, int* iterations) {
   const double eps = 1e-4, DT = 1e-1, damp = 1e-6; /* Kinematics.h:32-35 */
@@ -473,7 +473,7 @@ int orc_ik_inverse(const orc_ik* ik, const orc_pose* pose, const double* q0, int
     }
   }
   if (iterations) *iterations = it;
-  if (success) memcpy(q_out, q, sizeof(double) * nv);
+  memcpy(q_out, q, sizeof(double) * nv); /* (on failure: the last iterate, which Pin::inverse discards -- for the tests' twin rule) */
   return success;
 }
 
