@@ -1448,8 +1448,17 @@ RCSH_CONTACT_FN uint32_t contact_collide(const ContactTable& tab_, const CheckTa
       for (int k = 0; k < 3; ++k) arF[lane][9 + k] = p[k];
     }
   }
+  // ---- a pass that is here for geom PAIRS only (wave-uniform): box-less scene, slack record kept, the slack test above left pairs due and
+  // no geom due against the floor.  Every geom has height left above the floor, so the floor stage below would find nothing (it is
+  // skipped on `floor_due` already); the phantom box of a box-less scene has no size and is parked a kilometre up (rcs_hip.hip), so the
+  // box stage, the hulls' stage and the box-against-floor stage find nothing either: every count of the compaction is zero, every offset
+  // too.  Such a pass goes from the geoms' records straight to the pair tests; the contact list, its order and its keys are what
+  // the stages would have left, because all they would have added to it is nothing.  (ck.pad bit 6, RCSH_CHECK_SKIP=64: the stages run
+  // as before -- the switch the tests compare the two forms with.)
+  const bool pairs_only = remg && tab.has_plane && !b.present && !(ck.pad & 64) &&
+                          __ballot(lane < tab.ngeom && !(remf > 0.0f)) == 0;
   double bp[3], bR[9], bv[6];
-  box_frame(bs, bp, bR, bv);
+  if (!pairs_only) box_frame(bs, bp, bR, bv);
   __syncthreads();
   TEAM_MARK(37)  // (slots 37-39 here: the contact timing tool; the self-collision marks of the same slots are in kernels it does not launch)
   double ppos[4][3], pdist[4], cpos[8][3], cdist[8], cn[3] = {0, 0, 0};
@@ -1460,8 +1469,8 @@ RCSH_CONTACT_FN uint32_t contact_collide(const ContactTable& tab_, const CheckTa
   // (a pass that is here for a geom PAIR only -- every geom still has height left above the floor -- skips the floor tests: nothing can
   // touch it, and the heights keep what the slack test left of them)
   const bool floor_due = !remg || b.present || __ballot(has_geom && !(remf > 0.0f)) != 0;
-  if (has_geom) {
-    cg = tab.geoms[lane];
+  if (has_geom) cg = tab.geoms[lane];
+  if (has_geom && !pairs_only) {
     double Rl[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, pl[3] = {0, 0, 0};
     if (cg.link >= 0) {
 #pragma unroll
@@ -1562,7 +1571,7 @@ RCSH_CONTACT_FN uint32_t contact_collide(const ContactTable& tab_, const CheckTa
   // ---- the hulls' vertex work, one hull at a time with the whole wavefront: a lane scanning its hull's vertices in global
   // memory alone pays a memory round trip per vertex (its wavefront has nothing else to run); staged into LDS once, the
   // lanes of every 16-lane team scan every 16th vertex and agree on the winner -- the same vertex the serial scan finds.
-  {
+  if (!pairs_only) {
     __syncthreads();  // (the pads' clipping polygons in ar.stage are done with)
     TEAM_MARK(38)
     double* hv = &ar.stage[0][0];
@@ -1654,7 +1663,7 @@ RCSH_CONTACT_FN uint32_t contact_collide(const ContactTable& tab_, const CheckTa
   // the box against the floor (mjc_PlaneBox: corners in order, at most four)
   int nBP = 0;
   double bppos[4][3], bpdist[4];
-  if (tab.has_plane) {
+  if (tab.has_plane && !pairs_only) {
     const double dist = bp[2] - b.plane_z;
     for (int i = 0; i < 8 && nBP < 4; ++i) {
       const double vec[3] = {i & 1 ? b.size[0] : -b.size[0], i & 2 ? b.size[1] : -b.size[1], i & 4 ? b.size[2] : -b.size[2]};
@@ -1671,14 +1680,16 @@ RCSH_CONTACT_FN uint32_t contact_collide(const ContactTable& tab_, const CheckTa
     TEAM_MARK(25)
     return 0u;
   }
-  if (lane < 32) { ar.cnt[lane][0] = nP; ar.cnt[lane][1] = nB; }
-  __syncthreads();
-  TEAM_MARK(25)
   int offP = 0, offB = 0, totP = 0, totB = 0;
-  for (int g = 0; g < tab.ngeom; ++g) {
-    const int a = ar.cnt[g][0], c = ar.cnt[g][1];
-    if (g < lane) { offP += a; offB += c; }
-    totP += a; totB += c;
+  if (!pairs_only) {
+    if (lane < 32) { ar.cnt[lane][0] = nP; ar.cnt[lane][1] = nB; }
+    __syncthreads();
+    TEAM_MARK(25)
+    for (int g = 0; g < tab.ngeom; ++g) {
+      const int a = ar.cnt[g][0], c = ar.cnt[g][1];
+      if (g < lane) { offP += a; offB += c; }
+      totP += a; totB += c;
+    }
   }
   offB += totP + nBP;
   const int nreg_all = totP + nBP + totB;

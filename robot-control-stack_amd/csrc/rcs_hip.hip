@@ -224,7 +224,8 @@ Params make_params(rcsh_sim* s) {
   if (const char* dm = std::getenv("RCSH_CHECK_SKIP")) P.chk.pad = std::atoi(dm);  // development: bit 0 no narrow phase, 1 no boxes, 2 no spheres, 3 no
   // Gilbert fallback, 4 no slack record (timing experiments, check_team.h); bit 5 sends every coupled environment of a box-less scene to the
   // wide solve (contact_wide.h) whatever its contact count, not only those with more than kDenseCon contacts (contact_dense.h; the tests
-  // of the wide solve's math on few contacts, tests/test_gpu_contact_wide.py).  Read on every launch.
+  // of the wide solve's math on few contacts, tests/test_gpu_contact_wide.py); bit 6 takes the pairs-only shortcut out of the contact phase's
+  // collision pass (contact_team.h: contact_collide; tests/test_gpu_quiet_escalated.py compares the two forms).  Read on every launch.
   return P;
 }
 
@@ -2962,6 +2963,8 @@ extern "C" int rcsh_debug_check_cycles(unsigned long long* out16, int clear) {
   if (clear) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(rcsh::g_chk_cyc), z, sizeof(z)) != hipSuccess) return 1; }
   return 0;
 }
+#endif
+#if defined(RCSH_CHECK_DEBUG) || defined(RCSH_PHASE_TIMING)  // (the timing tools name the slack test's example pairs with it: tools/esc_timing.py)
 extern "C" int rcsh_debug_check_pairs(rcsh_sim* s, int32_t* g0g1 /* [cap][2] */, int32_t cap, int32_t* n, int32_t* nb) {
   *n = (int)s->tables.chk_pairs.size(); *nb = 0;
   for (int i = 0; i < *n && i < cap; ++i) { g0g1[2 * i] = s->cgeoms[s->tables.chk_pairs[i].g0].geom_id; g0g1[2 * i + 1] = s->cgeoms[s->tables.chk_pairs[i].g1].geom_id; }

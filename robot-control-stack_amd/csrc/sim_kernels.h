@@ -1487,6 +1487,7 @@ __device__ __attribute__((always_inline)) inline void run_team_body(const Params
       o[8] = success ? 1.0 : 0.0;
     }
   }
+  TEAM_MARK(46)  // (the epilogue's stores; 47: the end-of-launch check; 10: what is left, esc_finish)
   // ---- contacts nobody resolves (check_team.h): once per stepping launch, on the position the next position stage will see.
   // Everything of the launch is in HBM by now; the LDS block and the link records' memory are the check's workspace.
   if (do_check) {  // (wave-uniform)
@@ -1563,6 +1564,7 @@ __device__ __attribute__((always_inline)) inline void run_team_body(const Params
   } else if (esc_role == 2 && leader && have_frames && !esc_contact) {
     esc_leave = true;  // (no check in this launch: quiet is enough)
   }
+  TEAM_MARK(47)
   if (esc_role == 2) {
     if (esc_leave) atomicOr(reinterpret_cast<unsigned long long*>(lop.esc + 2 * ((P.n + 63) >> 6) + (e >> 6)), 1ull << (e & 63));
     esc_finish(lop, P.n);

@@ -6,9 +6,12 @@ import ctypes as C, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "robot-control-stack_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 import rcs_amd._lib as lib
-lib.LIB_PATH = os.path.join(ROOT, "robot-control-stack_amd", "rcs_amd", "librcs_hip_timing.so")
+lib.LIB_PATH = os.environ.get("RCSH_TIMING_LIB") or os.path.join(ROOT, "robot-control-stack_amd", "rcs_amd", "librcs_hip_timing.so")  # (RCSH_TIMING_LIB: another timing build, for A/B)
 import numpy as np
 import parity_util as PU
+_src = os.path.join(ROOT, "robot-control-stack_amd", "csrc")
+if os.path.getmtime(lib.LIB_PATH) < max(os.path.getmtime(os.path.join(_src, f)) for f in os.listdir(_src)):
+    raise SystemExit(f"{lib.LIB_PATH} is older than csrc/: rebuild it (tools/build_timing.sh)")
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 600
@@ -23,7 +26,7 @@ out = (C.c_ulonglong * 96)()
 def read():
     L.rcsh_debug_team_cycles96(out, 1)
     return np.array(out[:], dtype=np.float64)
-NAMES = {0: "pos stage", 1: "1", 2: "2", 3: "3", 4: "4", 15: "15", 5: "5", 6: "6", 7: "7", 8: "8", 9: "loop tail", 10: "epilogue+check", 11: "11", 12: "prologue12", 13: "13", 14: "14",
+NAMES = {0: "pos stage", 1: "1", 2: "2", 3: "3", 4: "4", 15: "15", 5: "5", 6: "6", 7: "7", 8: "8", 9: "loop tail", 10: "esc_finish+end", 46: "epilogue stores", 47: "end-of-launch check", 11: "11", 12: "prologue12", 13: "13", 14: "14",
          16: "collide before self", 17: "self broad", 18: "self narrow rest", 19: "self box-box", 20: "hull staging", 61: "Gilbert", 62: "portal refinement", 63: "hull records", 24: "before collide", 37: "link frames", 38: "lane per geom", 39: "hulls wavefront", 25: "floor/fastpath", 26: "compaction", 27: "rows/qacc_smooth/M", 28: "newton pre", 55: "x update", 48: "rows+grad",
          49: "stiffness", 50: "Hessian", 51: "row loads", 52: "LDL+solves", 53: "pre linesearch", 54: "linesearch", 30: "forces/Y/K", 31: "noslip rest", 40: "ns rel", 41: "ns owner", 44: "ns slots", 32: "results"}
 try:  # the geom pairs of the self-contact stage (index -> geoms), for the slack test's examples
