@@ -192,86 +192,4 @@ RCSH_HD void ldl6_solve(double* A, double* x) {
     for (int k = i + 1; k < 6; ++k) x[i] -= L[6 * k + i] * x[k];
 }
 
-// Pin::inverse.  `target` is the desired TCP pose in ROBOT coordinates, `tcp` the TCP offset, q is in/out
-// (arm angles; the model's remaining dofs are reported as 0 by the callers, reference quirk Q7).
-template <class T>
-RCSH_HD bool clik(const DevModel& m, const Pose& target, const Pose& tcp, double* q, int* iterations) {
-  // desired site placement in world coordinates: base * (target * tcp^-1)
-  Pose tinv, des_r, base, des;
-  pose_inverse(tcp, tinv);
-  pose_mul(target, tinv, des_r);
-  const double bq[4] = {m.base_quat[1], m.base_quat[2], m.base_quat[3], m.base_quat[0]};
-  pose_from_quat(bq, m.base_pos, base);
-  pose_mul(base, des_r, des);
-  double Rd[9];
-  quat_to_mat(des.q, Rd);
-  bool success = false;
-  int it = 0;
-  for (int i = 0;; ++i) {
-    double Rs[9], ps[3], ax[T::NARM][3], an[T::NARM][3];
-    site_fk<T>(m, q, Rs, ps, ax, an);
-    // iMd = frame^-1 * desired
-    double Ri[9], pi[3];
-    const double dp[3] = {des.t[0] - ps[0], des.t[1] - ps[1], des.t[2] - ps[2]};
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) Ri[3 * r + c] = Rs[r] * Rd[c] + Rs[3 + r] * Rd[3 + c] + Rs[6 + r] * Rd[6 + c];
-      pi[r] = Rs[r] * dp[0] + Rs[3 + r] * dp[1] + Rs[6 + r] * dp[2];
-    }
-    double err[6];
-    se3_log(Ri, pi, err);
-    it = i;
-    if (sqrt(dot6(err, err)) < kIkEps) { success = true; break; }
-    if (i >= kIkMaxIter) break;
-    // Jlog6 at iMd^-1
-    double Rt[9], pt[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) Rt[3 * r + c] = Ri[3 * c + r];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) pt[r] = -(Rt[3 * r] * pi[0] + Rt[3 * r + 1] * pi[1] + Rt[3 * r + 2] * pi[2]);
-    double Jlog[36];
-    se3_jlog(Rt, pt, Jlog);
-    // J <- -Jlog * J_local, column by column; accumulate J J^T
-    double JJ[T::NARM][6], JJt[36];
-#pragma unroll
-    for (int k = 0; k < 36; ++k) JJt[k] = 0.0;
-#pragma unroll
-    for (int j = 0; j < T::NARM; ++j) {
-      const double rr[3] = {ps[0] - an[j][0], ps[1] - an[j][1], ps[2] - an[j][2]};
-      double lin[3];
-      cross3(ax[j], rr, lin);
-      double col[6];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        col[k] = Rs[k] * lin[0] + Rs[3 + k] * lin[1] + Rs[6 + k] * lin[2];
-        col[3 + k] = Rs[k] * ax[j][0] + Rs[3 + k] * ax[j][1] + Rs[6 + k] * ax[j][2];
-      }
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        double s = 0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) s += Jlog[6 * r + k] * col[k];
-        JJ[j][r] = -s;
-      }
-#pragma unroll
-      for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) JJt[6 * r + c] += JJ[j][r] * JJ[j][c];
-    }
-#pragma unroll
-    for (int r = 0; r < 6; ++r) JJt[6 * r + r] += kIkDamp;
-    double y[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) y[k] = err[k];
-    ldl6_solve(JJt, y);
-#pragma unroll
-    for (int j = 0; j < T::NARM; ++j) q[j] += -dot6(JJ[j], y) * kIkDt;
-  }
-  if (iterations) *iterations = it;
-  return success;
-}
-
 }  // namespace rcsh

@@ -9,11 +9,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/rcs_hip.h"
 #include "model_host.h"
+#include "owned.h"
 #include "sim_kernels.h"
 #include "render.h"
 #include "query_team.h"
@@ -45,12 +48,18 @@ constexpr int kProfRing = 4096;
 int rcsh::episode_fail(int code, const char* msg) { return fail(code, msg); }  // (csrc/episode_host.cpp reports through rcsh_last_error)
 
 struct CopyCarrier;
+namespace {
+void copy_carrier_free(CopyCarrier* c);
+void rccl_comm_destroy(void* comm);
+}  // namespace
 // a buffer that grows on demand (grow_device / grow_pinned)
-struct Grown { void* p = nullptr; size_t cap = 0; };
+template <auto Release> struct Grown { Owned<void*, Release> p; size_t cap = 0; };
+using GrownDev = Grown<hipFree>;
+using GrownPin = Grown<hipHostFree>;
 // Device staging of the host-pointer entry points: one allocation, cut by stage_layout -- and nowhere else -- into typed slices that
 // do not overlap; each starts on a 256-byte boundary.  A slice with two names carries two contents that no single entry point uses together.
 struct Staging {
-  void* base = nullptr;
+  DevBuf<void> base;             // the slices below are views into it
   int action_w = 0, obs_w = 0, q0_w = 0;  // doubles per environment of `action`, `obs` and `q0`
   uint8_t* mask = nullptr;       // [n]: the caller's mask
   uint8_t* inv_mask = nullptr;   // [n]: its complement (observe_unmasked)
@@ -70,59 +79,66 @@ struct Staging {
 // Page-locked staging of the env layer's host forms, between the caller's arrays and the device slices (offsets in bytes):
 // [action | gripper | box pose | obs | info | gripper width | substeps | task]
 struct PinLayout { size_t action, gripper, box, obs, info, gw, sub, task, total; };
+// Who owns what: every buffer, stream and event the handle creates lives in an owner (owned.h) below and goes when the handle is
+// deleted -- members in reverse order, so own_stream, declared before every buffer, goes last.  An entry point that replaces or first
+// creates a GROUP of resources builds it in local owners and moves it in after the last step that can fail: on failure the handle
+// is what it was before the call.  Device-visible structs (Params, RunOp, RendCfg, RenderScene, ...) are filled from get().
 struct rcsh_sim {
   int device = 0;
   int kernel = RCSH_KERNEL_AUTO;
   int n_simd = 1024;  // SIMDs of the device (4 per compute unit)
-  hipStream_t stream = nullptr;
-  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;  // view: own_stream, or the caller's (rcsh_sim_set_stream)
+  Stream own_stream;
   int n = 0;
   HostModel hm;
   DevModel dm;
-  DevModel* d_model = nullptr;     // DevModel followed by LinkRec[kMaxLinks]
+  DevBuf<DevModel> d_model;        // DevModel followed by LinkRec[kMaxLinks]
   std::vector<LinkRec> links;
   CollisionPoints cp;
   std::vector<uint8_t> cp_class;
-  double* d_coll_xyzr = nullptr;
-  uint8_t* d_coll_cls = nullptr;
+  DevBuf<double> d_coll_xyzr;
+  DevBuf<uint8_t> d_coll_cls;
   // contact phase (contact_team.h): the robot's collision geoms and their hull vertices
   std::vector<ContactGeom> cgeoms;
   std::string contact_overflow;  // why collision geoms were left out of `cgeoms` (capacity); empty: none were
   std::vector<int> cgeoms_dropped;  // mjModel ids of those geoms: invisible to geom-geom detection (the floor test by sample points still sees them)
   std::vector<double> cverts;
-  ContactGeom* d_cgeoms = nullptr;
-  double* d_cverts = nullptr;
+  DevBuf<ContactGeom> d_cgeoms;
+  DevBuf<double> d_cverts;
   // what the collision tests may skip (model.cpp: build_collision_tables; rebuilt when the class bits change) and its device copies: the
   // self-collision pairs a collision callback reacts to; the once-per-launch check for contacts nobody resolves (check_team.h)
   CollisionTables tables;
-  Grown d_pairs, d_chk_ent, d_chk_geoms;  // SelfPair[], CheckEntry[], CheckGeom[]
-  float* d_lev = nullptr;            // tables.link_lever
-  float* d_slack = nullptr;          // [n][kSlackStride]: the self-contact stage's remaining gaps per pair + the joints it saw last (CheckTable::slack)
-  Grown d_query;                     // staging of the host-pointer collision queries (rcsh_collision_query / rcsh_motion_query) and of the peek's action
+  GrownDev d_pairs, d_chk_ent, d_chk_geoms;  // SelfPair[], CheckEntry[], CheckGeom[]
+  DevBuf<float> d_lev;               // tables.link_lever
+  DevBuf<float> d_slack;             // [n][kSlackStride]: the self-contact stage's remaining gaps per pair + the joints it saw last (CheckTable::slack)
+  GrownDev d_query;                  // staging of the host-pointer collision queries (rcsh_collision_query / rcsh_motion_query) and of the peek's action
   // the environments' collision guard (guard_team.h; rcsh_env_configure_guard): its settings, and two records of [result | t_contact |
-  // blocked | hold] -- the last guarded step's (rcsh_env_guard_last) and the scratch of rcsh_env_guard_peek
+  // blocked | hold] -- the last guarded step's (rcsh_env_guard_last) and the scratch of rcsh_env_guard_peek.  d_guard and h_guard are
+  // one group, present or absent together; so are d_episode and h_episode below.
   struct GuardCfg { bool configured = false, enabled = false, block_undecided = true, truncate = true; int kinds = 0; double resolution = 0; } guard;
-  void* d_guard = nullptr;
+  DevBuf<void> d_guard;
   bool guard_stepped = false;        // a guarded step has filled the first record
-  char* h_guard = nullptr;           // page-locked copy of that record: rcsh_env_step fetches it with its own outputs (one synchronisation)
+  PinBuf<char> h_guard;              // page-locked copy of that record: rcsh_env_step fetches it with its own outputs (one synchronisation)
   bool guard_host_valid = false;     // ... and it is the last guarded step's
   // autoreset (episode_team.h; rcsh_env_configure_autoreset): the description, the record every step under autoreset rewrites
   // (EpisodeLayout), and a page-locked copy of the record's front (verdict bytes, returns, lengths) that the host forms of env.step
   // fetch with their own outputs
   struct AutoresetCfg { bool configured = false, enabled = false; rcsh_autoreset_desc desc{}; } autoreset;
-  void* d_episode = nullptr;
-  char* h_episode = nullptr;
+  DevBuf<void> d_episode;
+  PinBuf<char> h_episode;
   bool episode_stepped = false;      // a step under autoreset has filled the record
   bool episode_host_valid = false;   // ... and h_episode is that step's
   // per-environment escalation (sim_kernels.h: RunOp::esc_role): a step is the lean launch over the environments not in contact plus
   // the contact-resolving launch over the others
   bool esc_mode = false;
-  uint64_t* d_esc = nullptr;       // [3][(n + 63) / 64]: escalated, newly flagged, leaving
-  uint32_t* d_esc_ctr = nullptr;   // [4] (sim_kernels.h: RunOp::esc_ctr)
+  struct EscBufs {                 // one group, present or absent together (rcsh_sim_set_contact_options)
+    DevBuf<uint64_t> mask;         // [3][(n + 63) / 64]: escalated, newly flagged, leaving
+    DevBuf<uint32_t> ctr;          // [4] (sim_kernels.h: RunOp::esc_ctr)
+    DevBuf<double> snap;           // [nfields][n]: what the lean launch of a step read (the step is redone from it on a hit)
+    DevBuf<uint32_t> snap_flags;
+    DevBuf<int32_t> snap_conv;
+  } esc;
   int conv_chunk = 48;              // step_until_convergence in pieces of this many substeps when contacts are resolved per environment (launch_run; RCSH_CONV_CHUNK)
-  double* d_snap = nullptr;        // [nfields][n]: what the lean launch of a step read (the step is redone from it on a hit)
-  uint32_t* d_snap_flags = nullptr;
-  int32_t* d_snap_conv = nullptr;
   bool contact_check = true;  // RCSH_CONTACT_CHECK=0 switches the check off (measurements of its cost)
   int check_every = 1;        // the check ends every check_every-th stepping launch (rcsh_sim_set_contact_check); 0: never
   int64_t check_seq = 0;
@@ -131,9 +147,9 @@ struct rcsh_sim {
   int narm = 0, nl = 0, nu = 0;
   bool grip = false;
   int nfields = 0;
-  double* S = nullptr;
-  uint32_t* flags = nullptr;
-  int32_t* conv = nullptr;
+  DevBuf<double> S;
+  DevBuf<uint32_t> flags;
+  DevBuf<int32_t> conv;
   SimCfg sim{0, 0, 30, 500};
   RobotCfg robot{};
   GripperCfg gripcfg{};
@@ -141,45 +157,51 @@ struct rcsh_sim {
   BoxCfg box{};
   TaskCfg task{};
   bool env_configured = false;
-  BoxTaskCfg* d_boxtask = nullptr;
+  DevBuf<BoxTaskCfg> d_boxtask;
   // depth renderer (render.h)
-  RenderScene rscene{};
-  RenderShape* d_rshapes = nullptr;
-  double* d_rplanes = nullptr;
-  RenderColour* d_rcolours = nullptr;
-  int32_t* d_redge_planes = nullptr;  // the outline method of the ray caster (render.h: k_hull_views)
-  double* d_redge_verts = nullptr;
-  double* d_rviews = nullptr;
-  RendCfg rend{};                    // rate-driven cameras (rcsh_sim_set_render_schedule)
+  RenderScene rscene{};              // its pointers are views into rbuf (rcsh_sim_set_render_scene, rcsh_sim_set_render_colours)
+  struct RenderBufs {                // one group: a scene's buffers are replaced together
+    DevBuf<RenderShape> shapes;
+    DevBuf<double> planes;
+    DevBuf<RenderColour> colours;
+    DevBuf<int32_t> edge_planes;     // the outline method of the ray caster (render.h: k_hull_views)
+    DevBuf<double> edge_verts, views;
+    DevBuf<double> frames;           // present: a render scene is attached
+    DevBuf<double> wframes;          // world frames of the shapes + camera per environment (k_shape_frames)
+  } rbuf;
+  RendCfg rend{};                    // rate-driven cameras (rcsh_sim_set_render_schedule); its pointers are views into the three owners
+  DevBuf<double> rend_last, rend_snap;
+  DevBuf<int32_t> rend_count;
   int rend_cam_id[kMaxRateCams] = {0, 0, 0, 0};
   int64_t rend_dropped = 0;          // records that did not fit the schedule's capacity (rcsh_render_pending counts them)
-  const double* frames_src = nullptr; // set while a record of the render schedule is being rendered
+  const double* frames_src = nullptr; // view into rend_snap, set while a record of the render schedule is being rendered
   const double* frames_src_base(int slot) const { return rend.snap + (size_t)slot * (size_t)(nl + 9) * (size_t)n; }
-  double* d_frames = nullptr;
-  double* d_wframes = nullptr;  // world frames of the shapes + camera per environment (k_shape_frames)
   bool render_f64 = false;      // the ray caster's arithmetic type (rcsh_sim_set_render_f64; RCSH_RENDER_F64=1 at creation)
   std::vector<RenderCam> cams;
-  Grown d_image;  // staging for the host-pointer render call
-  double* pending_task = nullptr;  // task output of the env-step being enqueued (rcsh_env_step_task*)
+  GrownDev d_image;  // staging for the host-pointer render call
+  double* pending_task = nullptr;  // view into the caller's memory or the staging: task output of the env-step being enqueued (rcsh_env_step_task*)
   // staging for the host-pointer entry points: the device side, fixed at creation (stage_create), and page-locked memory between it and
   // the caller's arrays for the env layer's host forms (PinLayout; a copy to or from pageable memory is staged by the runtime and waited
   // for, one array at a time: 0.19 of rcsh_env_step's 0.32 ms)
   Staging stage;
   PinLayout pin{};
-  Grown h_pin;
-  // multi-GPU exchange (RCCL, loaded on first use)
-  void* comm = nullptr;            // ncclComm_t
-  hipStream_t comm_stream = nullptr;
-  hipEvent_t comm_ready = nullptr, comm_done[2] = {nullptr, nullptr};
-  bool comm_pending[2] = {false, false};
-  int comm_rank = 0, comm_world = 1;
-  struct CopyCarrier* copy = nullptr;  // the all-gather's second carrier: copy engines + flags in peer memory (rcsh_comm_copy_*)
+  GrownPin h_pin;
+  // multi-GPU exchange: built in a local by rcsh_comm_init / rcsh_comm_copy_create and attached whole; rcsh_comm_destroy is its one
+  // teardown.  Destroyed in reverse: the carrier or the communicator, the events, the stream.
+  struct Comm {
+    Stream stream;
+    Event ready, done[2];
+    Owned<void*, rccl_comm_destroy> nccl;          // ncclComm_t (RCCL, loaded on first use)
+    Owned<CopyCarrier*, copy_carrier_free> copy;   // the all-gather's second carrier: copy engines + flags in peer memory (rcsh_comm_copy_*)
+    bool pending[2] = {false, false};
+    int rank = 0, world = 1;
+  } comm;
   // profiling
-  hipEvent_t order_ev = nullptr;       // rcsh_sim_wait_for: marks this handle's stream for another handle's stream to wait on
+  Event order_ev;                      // rcsh_sim_wait_for: marks this handle's stream for another handle's stream to wait on
   bool prof = false;
   bool prof_region = false;            // one event pair around the whole timed region instead of sampled launches
   int64_t prof_region_launches = 0;
-  std::vector<hipEvent_t> ev_start, ev_stop;
+  std::vector<Event> ev_start, ev_stop;
   int prof_pending = 0;
   int prof_every = 1;       // HIP events around every prof_every-th stepping launch
   int64_t prof_seen = 0;
@@ -195,32 +217,32 @@ int grid_for(int n) { return (n + kBlock - 1) / kBlock; }
 Params make_params(rcsh_sim* s) {
   const CollisionTables& t = s->tables;
   Params P;
-  P.model = s->d_model;
+  P.model = s->d_model.get();
   std::memcpy(&P.coll, &t.coll, sizeof(P.coll));
-  P.coll.xyzr = s->d_coll_xyzr;
-  P.coll.cls = s->d_coll_cls;
-  P.S = s->S;
-  P.flags = s->flags;
-  P.conv_steps = s->conv;
+  P.coll.xyzr = s->d_coll_xyzr.get();
+  P.coll.cls = s->d_coll_cls.get();
+  P.S = s->S.get();
+  P.flags = s->flags.get();
+  P.conv_steps = s->conv.get();
   P.n = s->n;
-  P.keep_qpre = s->d_frames != nullptr;
+  P.keep_qpre = bool(s->rbuf.frames);
   P.sim = s->sim;
   P.robot = s->robot;
   P.grip = s->gripcfg;
   P.env = s->env;
-  P.boxtask = s->d_boxtask;
+  P.boxtask = s->d_boxtask.get();
   P.rend = s->rend;
   std::memcpy(&P.ctab, &t.ctab, sizeof(P.ctab));
-  P.ctab.geoms = s->d_cgeoms;
-  P.ctab.verts = s->d_cverts;
-  P.ctab.pairs = static_cast<const SelfPair*>(s->d_pairs.p);
+  P.ctab.geoms = s->d_cgeoms.get();
+  P.ctab.verts = s->d_cverts.get();
+  P.ctab.pairs = static_cast<const SelfPair*>(s->d_pairs.p.get());
   P.ctab.ngeom = s->box.resolve ? (int)s->cgeoms.size() : 0;
   P.ctab.plane_mu = s->plane_mu;
   std::memcpy(&P.chk, &t.chk, sizeof(P.chk));
-  P.chk.ent = static_cast<const CheckEntry*>(s->d_chk_ent.p);
-  P.chk.lev = s->d_lev;
-  P.chk.geoms = static_cast<const CheckGeom*>(s->d_chk_geoms.p);
-  P.chk.slack = s->d_slack;
+  P.chk.ent = static_cast<const CheckEntry*>(s->d_chk_ent.p.get());
+  P.chk.lev = s->d_lev.get();
+  P.chk.geoms = static_cast<const CheckGeom*>(s->d_chk_geoms.p.get());
+  P.chk.slack = s->d_slack.get();
   if (const char* dm = std::getenv("RCSH_CHECK_SKIP")) P.chk.pad = std::atoi(dm);  // development: bit 0 no narrow phase, 1 no boxes, 2 no spheres, 3 no
   // Gilbert fallback, 4 no slack record (timing experiments, check_team.h); bit 5 sends every coupled environment of a box-less scene to the
   // wide solve (contact_wide.h) whatever its contact count, not only those with more than kDenseCon contacts (contact_dense.h; the tests
@@ -231,18 +253,18 @@ Params make_params(rcsh_sim* s) {
 
 int upload_boxtask(rcsh_sim* s) {
   BoxTaskCfg bt{s->box, s->task};
-  if (!s->d_boxtask) HIP_TRY(hipMalloc(&s->d_boxtask, sizeof(BoxTaskCfg)));
-  HIP_TRY(hipMemcpyAsync(s->d_boxtask, &bt, sizeof(bt), hipMemcpyHostToDevice, s->stream));
+  if (!s->d_boxtask) HIP_TRY(hipMalloc(s->d_boxtask.out(), sizeof(BoxTaskCfg)));
+  HIP_TRY(hipMemcpyAsync(s->d_boxtask.get(), &bt, sizeof(bt), hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RCSH_OK;
 }
 
 int upload_model(rcsh_sim* s) {
-  HIP_TRY(hipMemcpyAsync(s->d_model, &s->dm, sizeof(DevModel), hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->d_model.get(), &s->dm, sizeof(DevModel), hipMemcpyHostToDevice, s->stream));
   // the team kernels' per-link records live right behind the DevModel
   s->links.resize(kMaxLinks);
   fill_link_records(s->dm, s->links.data());
-  HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(s->d_model) + sizeof(DevModel), s->links.data(), sizeof(LinkRec) * kMaxLinks,
+  HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(s->d_model.get()) + sizeof(DevModel), s->links.data(), sizeof(LinkRec) * kMaxLinks,
                          hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RCSH_OK;
@@ -251,7 +273,7 @@ int upload_model(rcsh_sim* s) {
 // class bits of the contact sample points: bit 0 arm collision geoms, bit 1 gripper collision geoms
 int upload_coll_classes(rcsh_sim* s) {
   if (s->cp.geom.empty()) return RCSH_OK;
-  HIP_TRY(hipMemcpyAsync(s->d_coll_cls, s->cp_class.data(), s->cp_class.size(), hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->d_coll_cls.get(), s->cp_class.data(), s->cp_class.size(), hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RCSH_OK;
 }
@@ -259,26 +281,22 @@ int upload_coll_classes(rcsh_sim* s) {
 static_assert(kSelfStageVertsHost == kSelfStageVerts, "the pair filter's vertex cap is the self-contact stage's LDS room (contact_team.h)");
 
 // one buffer, grown on demand: the stream may still be reading or writing the old one
-int grow(rcsh_sim* s, Grown& g, size_t bytes, bool pinned) {
+template <class G, class Alloc>
+int grow(rcsh_sim* s, G& g, size_t bytes, Alloc alloc) {
   if (bytes <= g.cap) return RCSH_OK;
-  if (g.p) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    void* old = g.p;
-    g = Grown{};
-    HIP_TRY(pinned ? hipHostFree(old) : hipFree(old));
-  }
-  void* p = nullptr;
-  HIP_TRY(pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes));
-  g.p = p; g.cap = bytes;
+  if (g.p) HIP_TRY(hipStreamSynchronize(s->stream));
+  g.cap = 0;
+  HIP_TRY(alloc(g.p.out(), bytes));
+  g.cap = bytes;
   return RCSH_OK;
 }
-int grow_device(rcsh_sim* s, Grown& g, size_t bytes) { return grow(s, g, bytes, false); }
-int grow_pinned(rcsh_sim* s, Grown& g, size_t bytes) { return grow(s, g, bytes, true); }
+int grow_device(rcsh_sim* s, GrownDev& g, size_t bytes) { return grow(s, g, bytes, [](void** p, size_t b) { return hipMalloc(p, b); }); }
+int grow_pinned(rcsh_sim* s, GrownPin& g, size_t bytes) { return grow(s, g, bytes, [](void** p, size_t b) { return hipHostMalloc(p, b, hipHostMallocDefault); }); }
 
 // a host table's device copy; the buffer grows on demand (grow_device waits for the stream before it frees one a launch may still read)
-int upload(rcsh_sim* s, Grown& g, const void* src, size_t bytes) {
+int upload(rcsh_sim* s, GrownDev& g, const void* src, size_t bytes) {
   if (int rc = grow_device(s, g, bytes)) return rc;
-  if (bytes) HIP_TRY(hipMemcpyAsync(g.p, src, bytes, hipMemcpyHostToDevice, s->stream));
+  if (bytes) HIP_TRY(hipMemcpyAsync(g.p.get(), src, bytes, hipMemcpyHostToDevice, s->stream));
   return RCSH_OK;
 }
 
@@ -291,13 +309,13 @@ int upload_contact_table(rcsh_sim* s) {
   if (!rc) rc = upload(s, s->d_chk_ent, t.chk_ent.data(), sizeof(CheckEntry) * t.chk_ent.size());
   if (!rc) rc = upload(s, s->d_chk_geoms, t.chk_geoms.data(), sizeof(CheckGeom) * t.chk_geoms.size());
   if (rc) return rc;
-  if (!s->d_lev) HIP_TRY(hipMalloc(&s->d_lev, sizeof(t.link_lever)));
-  HIP_TRY(hipMemcpyAsync(s->d_lev, t.link_lever, sizeof(t.link_lever), hipMemcpyHostToDevice, s->stream));
-  if (!s->d_cgeoms) HIP_TRY(hipMalloc(&s->d_cgeoms, sizeof(ContactGeom) * s->cgeoms.size()));
-  HIP_TRY(hipMemcpyAsync(s->d_cgeoms, s->cgeoms.data(), sizeof(ContactGeom) * s->cgeoms.size(), hipMemcpyHostToDevice, s->stream));
+  if (!s->d_lev) HIP_TRY(hipMalloc(s->d_lev.out(), sizeof(t.link_lever)));
+  HIP_TRY(hipMemcpyAsync(s->d_lev.get(), t.link_lever, sizeof(t.link_lever), hipMemcpyHostToDevice, s->stream));
+  if (!s->d_cgeoms) HIP_TRY(hipMalloc(s->d_cgeoms.out(), sizeof(ContactGeom) * s->cgeoms.size()));
+  HIP_TRY(hipMemcpyAsync(s->d_cgeoms.get(), s->cgeoms.data(), sizeof(ContactGeom) * s->cgeoms.size(), hipMemcpyHostToDevice, s->stream));
   if (!s->d_cverts && !s->cverts.empty()) {
-    HIP_TRY(hipMalloc(&s->d_cverts, sizeof(double) * s->cverts.size()));
-    HIP_TRY(hipMemcpyAsync(s->d_cverts, s->cverts.data(), sizeof(double) * s->cverts.size(), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMalloc(s->d_cverts.out(), sizeof(double) * s->cverts.size()));
+    HIP_TRY(hipMemcpyAsync(s->d_cverts.get(), s->cverts.data(), sizeof(double) * s->cverts.size(), hipMemcpyHostToDevice, s->stream));
   }
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RCSH_OK;
@@ -306,8 +324,8 @@ int upload_contact_table(rcsh_sim* s) {
 int prof_flush(rcsh_sim* s) {
   for (int i = 0; i < s->prof_pending; ++i) {
     float ms = 0;
-    HIP_TRY(hipEventSynchronize(s->ev_stop[i]));
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev_start[i], s->ev_stop[i]));
+    HIP_TRY(hipEventSynchronize(s->ev_stop[i].get()));
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev_start[i].get(), s->ev_stop[i].get()));
     s->prof_ms += ms;
   }
   s->prof_launches += s->prof_pending;
@@ -370,7 +388,7 @@ int launch_run_once(rcsh_sim* s, const RunOp& op_in, bool timed) {
   hipError_t err = hipSuccess;
   if (timed && s->prof_region) {
     // region mode: one event before the first timed launch, one after the last (rcsh_prof_read): no event traffic in between
-    if (s->prof_region_launches == 0) HIP_TRY(hipEventRecord(s->ev_start[0], s->stream));
+    if (s->prof_region_launches == 0) HIP_TRY(hipEventRecord(s->ev_start[0].get(), s->stream));
     s->prof_region_launches++;
   }
   const bool sample = timed && s->prof && !s->prof_region && (s->prof_seen++ % s->prof_every) == 0;
@@ -379,7 +397,7 @@ int launch_run_once(rcsh_sim* s, const RunOp& op_in, bool timed) {
       int rc = prof_flush(s);
       if (rc) return rc;
     }
-    HIP_TRY(hipEventRecord(s->ev_start[s->prof_pending], s->stream));
+    HIP_TRY(hipEventRecord(s->ev_start[s->prof_pending].get(), s->stream));
   }
   // k_run_team: 16 lanes per environment, 4 environments per wavefront.  4096 environments are 1024 wavefronts = one per
   // SIMD of the chip.  (A one-lane-per-environment kernel existed through round 1; it lost at every batch size and could
@@ -391,8 +409,8 @@ int launch_run_once(rcsh_sim* s, const RunOp& op_in, bool timed) {
   // per-environment escalation: stepping launches of a box-less scene whose robot contacts are resolved environment by environment
   const bool esc = s->esc_mode && s->box.resolve && !s->box.present && (op.nsteps != 0 || op.do_reset) && !op.observe_only;
   if (esc) {
-    op.esc = s->d_esc; op.esc_ctr = s->d_esc_ctr;
-    op.snap = s->d_snap; op.snap_flags = s->d_snap_flags; op.snap_conv = s->d_snap_conv;
+    op.esc = s->esc.mask.get(); op.esc_ctr = s->esc.ctr.get();
+    op.snap = s->esc.snap.get(); op.snap_flags = s->esc.snap_flags.get(); op.snap_conv = s->esc.snap_conv.get();
   }
   bool launched = false;
   bool ok = dispatch_topology(s->narm, s->grip, [&](auto topo) {
@@ -451,7 +469,7 @@ int launch_run_once(rcsh_sim* s, const RunOp& op_in, bool timed) {
   if (!ok || !launched) return fail(RCSH_ERR_MODEL, "no kernel instantiated for this archetype");
   if (err != hipSuccess) return fail(RCSH_ERR_DEVICE, std::string("k_run launch: ") + hipGetErrorString(err));
   if (sample) {
-    HIP_TRY(hipEventRecord(s->ev_stop[s->prof_pending], s->stream));
+    HIP_TRY(hipEventRecord(s->ev_stop[s->prof_pending].get(), s->stream));
     s->prof_pending++;
   }
   return RCSH_OK;
@@ -523,8 +541,8 @@ int stage_create(rcsh_sim* s) {
   st.obs_w = kObsBase + s->narm;
   st.q0_w = s->narm;
   if (s->nl > st.obs_w) return fail(RCSH_ERR_MODEL, "the inverse kinematics' output (nq wide) does not fit the observations' staging slice");
-  HIP_TRY(hipMalloc(&st.base, stage_layout(st, n, 0)));
-  stage_layout(st, n, reinterpret_cast<uintptr_t>(st.base));
+  HIP_TRY(hipMalloc(st.base.out(), stage_layout(st, n, 0)));
+  stage_layout(st, n, reinterpret_cast<uintptr_t>(st.base.get()));
   size_t o = 0;
   auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 63) & ~size_t(63); return at; };
   PinLayout& L = s->pin;
@@ -548,6 +566,13 @@ int upload_mask(rcsh_sim* s, const uint8_t* mask, const uint8_t** dev) {
   return RCSH_OK;
 }
 
+// The state was written from outside the stepping launches (set_joints_hard, mjData.qpos = ..., a snapshot, another contact option) and
+// the robot may have moved: the gaps the contact check and the contact phase remember for the old position are void; zero = "look at everything".
+int void_remembered_gaps(rcsh_sim* s) {
+  if (s->d_slack) HIP_TRY(hipMemsetAsync(s->d_slack.get(), 0, sizeof(float) * (size_t)kSlackStride * s->n, s->stream));
+  return RCSH_OK;
+}
+
 // host [n][width] -> state fields
 int scatter_host(rcsh_sim* s, int field0, int width, const double* src, const uint8_t* mask) {
   if (width > kStageWidth) return fail(RCSH_ERR_ARG, "scatter_host: field group wider than the staging buffer");
@@ -555,10 +580,8 @@ int scatter_host(rcsh_sim* s, int field0, int width, const double* src, const ui
   int rc = upload_mask(s, mask, &dm);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(s->stage.wide, src, sizeof(double) * s->n * width, hipMemcpyHostToDevice, s->stream));
-  // (a write into the state from outside the stepping launches -- set_joints_hard, mjData.qpos = ... -- may move the robot: the gaps the
-  // contact check and the contact phase remember for the old position are void; zero = "look at everything")
-  if (s->d_slack) HIP_TRY(hipMemsetAsync(s->d_slack, 0, sizeof(float) * (size_t)kSlackStride * s->n, s->stream));
-  hipLaunchKernelGGL(k_scatter, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->S, s->n, field0, width, s->stage.wide, dm);
+  if ((rc = void_remembered_gaps(s))) return rc;
+  hipLaunchKernelGGL(k_scatter, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->S.get(), s->n, field0, width, s->stage.wide, dm);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RCSH_OK;
@@ -566,7 +589,7 @@ int scatter_host(rcsh_sim* s, int field0, int width, const double* src, const ui
 
 int gather_host(rcsh_sim* s, int field0, int width, double* dst) {
   if (width > kStageWidth) return fail(RCSH_ERR_ARG, "gather_host: field group wider than the staging buffer");
-  hipLaunchKernelGGL(k_gather, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, (const double*)s->S, s->n, field0, width, s->stage.wide);
+  hipLaunchKernelGGL(k_gather, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, (const double*)s->S.get(), s->n, field0, width, s->stage.wide);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(dst, s->stage.wide, sizeof(double) * s->n * width, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -575,7 +598,7 @@ int gather_host(rcsh_sim* s, int field0, int width, double* dst) {
 
 int flag_host(rcsh_sim* s, uint32_t bit, uint8_t* dst) {
   if (!dst) return RCSH_OK;
-  hipLaunchKernelGGL(k_flags_to_bytes, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, (const uint32_t*)s->flags, s->n, bit, s->stage.flag);
+  hipLaunchKernelGGL(k_flags_to_bytes, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, (const uint32_t*)s->flags.get(), s->n, bit, s->stage.flag);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(dst, s->stage.flag, s->n, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -588,7 +611,7 @@ int flags_update_host(rcsh_sim* s, uint32_t set, uint32_t clear, const uint8_t* 
   const uint8_t* dm = nullptr;
   int rc = upload_mask(s, mask, &dm);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_flags_update, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->flags, s->n, set, clear, dm);
+  hipLaunchKernelGGL(k_flags_update, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->flags.get(), s->n, set, clear, dm);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RCSH_OK;
@@ -652,7 +675,7 @@ EpisodeLayout episode_layout(const rcsh_sim* s) {
 // the page-locked buffer (laid out by rcsh_sim::pin), allocated at its first use
 int pin_ready(rcsh_sim* s, char*& h) {
   int rc = grow_pinned(s, s->h_pin, s->pin.total);
-  h = static_cast<char*>(s->h_pin.p);
+  h = static_cast<char*>(s->h_pin.p.get());
   return rc;
 }
 // host array -> page-locked memory -> device slice, enqueued (the entry point's closing wait covers it)
@@ -678,8 +701,8 @@ int fetch_env_outputs(rcsh_sim* s, const EnvOut& out, bool guard_record_too, boo
       {out.task, st.box_task, L.task, sizeof(double) * n * kTaskWidth}};
   for (const auto& p : pieces)
     if (p.dst) HIP_TRY(hipMemcpyAsync(h + p.at, p.src, p.bytes, hipMemcpyDeviceToHost, s->stream));
-  if (guard_record_too) HIP_TRY(hipMemcpyAsync(s->h_guard, s->d_guard, guard_layout(s).host_bytes, hipMemcpyDeviceToHost, s->stream));
-  if (episode_record_too) HIP_TRY(hipMemcpyAsync(s->h_episode, s->d_episode, episode_layout(s).host_bytes, hipMemcpyDeviceToHost, s->stream));
+  if (guard_record_too) HIP_TRY(hipMemcpyAsync(s->h_guard.get(), s->d_guard.get(), guard_layout(s).host_bytes, hipMemcpyDeviceToHost, s->stream));
+  if (episode_record_too) HIP_TRY(hipMemcpyAsync(s->h_episode.get(), s->d_episode.get(), episode_layout(s).host_bytes, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   for (const auto& p : pieces)
     if (p.dst) std::memcpy(p.dst, h + p.at, p.bytes);
@@ -719,101 +742,73 @@ int rcsh_sim_create(const rcsh_model_desc* model, int32_t n_envs, int32_t device
   if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
     return fail(RCSH_ERR_DEVICE, "no HIP device available: the batched backend has no CPU path");
   if (device < 0 || device >= count) return fail(RCSH_ERR_DEVICE, "device index out of range");
-  rcsh_sim* s = new rcsh_sim();
+  struct Destroy { void operator()(rcsh_sim* s) const { rcsh_sim_destroy(s); } };
+  std::unique_ptr<rcsh_sim, Destroy> owner(new rcsh_sim());  // (every return before the last destroys the half-built handle)
+  rcsh_sim* s = owner.get();
+  s->device = device;
   s->hm.copy_from(*model);
   std::string why = finalize_model(s->hm, s->dm, s->act_slot);
-  if (!why.empty()) {
-    delete s;
-    return fail(RCSH_ERR_MODEL, why);
-  }
-  s->device = device;
+  if (!why.empty()) return fail(RCSH_ERR_MODEL, why);
   s->n = n_envs;
   s->narm = s->dm.narm; s->nl = s->dm.nl; s->grip = s->dm.has_gripper != 0;
   s->nu = s->narm + (s->grip ? 1 : 0);
   s->nfields = with_layout(s, [&](auto topo) { return (int)Lay<decltype(topo)>::COUNT; });
-  auto cleanup = [&](int code, const std::string& msg) {
-    rcsh_sim_destroy(s);
-    return fail(code, msg);
-  };
-#define HIP_NEW(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t _e = (expr);                                                            \
-    if (_e != hipSuccess) return cleanup(RCSH_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-  HIP_NEW(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) s->n_simd = 4 * cus;
   }
-  HIP_NEW(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
-  s->stream = s->own_stream;
+  HIP_TRY(hipStreamCreateWithFlags(s->own_stream.out(), hipStreamNonBlocking));
+  s->stream = s->own_stream.get();
   const size_t n = (size_t)n_envs;
-  HIP_NEW(hipMalloc(&s->d_model, sizeof(DevModel) + sizeof(LinkRec) * kMaxLinks));
+  HIP_TRY(hipMalloc(s->d_model.out(), sizeof(DevModel) + sizeof(LinkRec) * kMaxLinks));
   {
     std::string cwhy = build_collision_points(s->hm, s->cp);
-    if (!cwhy.empty()) return cleanup(RCSH_ERR_MODEL, cwhy);
+    if (!cwhy.empty()) return fail(RCSH_ERR_MODEL, cwhy);
     s->cp_class.assign(s->cp.geom.size(), 0);
     cwhy = build_contact_table(s->hm, s->dm, s->cp.has_plane ? s->cp.plane_geom : -1, s->cgeoms, s->cverts, s->contact_overflow, &s->cgeoms_dropped);
-    if (!cwhy.empty()) return cleanup(RCSH_ERR_MODEL, cwhy);
+    if (!cwhy.empty()) return fail(RCSH_ERR_MODEL, cwhy);
     if (s->cp.has_plane) s->plane_mu = s->hm.geom_friction[3 * (size_t)s->cp.plane_geom];
     if (!s->cp.geom.empty()) {
-      HIP_NEW(hipMalloc(&s->d_coll_xyzr, sizeof(double) * s->cp.xyzr.size()));
-      HIP_NEW(hipMalloc(&s->d_coll_cls, s->cp_class.size()));
-      HIP_NEW(hipMemcpy(s->d_coll_xyzr, s->cp.xyzr.data(), sizeof(double) * s->cp.xyzr.size(), hipMemcpyHostToDevice));
-      HIP_NEW(hipMemcpy(s->d_coll_cls, s->cp_class.data(), s->cp_class.size(), hipMemcpyHostToDevice));
+      HIP_TRY(hipMalloc(s->d_coll_xyzr.out(), sizeof(double) * s->cp.xyzr.size()));
+      HIP_TRY(hipMalloc(s->d_coll_cls.out(), s->cp_class.size()));
+      HIP_TRY(hipMemcpy(s->d_coll_xyzr.get(), s->cp.xyzr.data(), sizeof(double) * s->cp.xyzr.size(), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(s->d_coll_cls.get(), s->cp_class.data(), s->cp_class.size(), hipMemcpyHostToDevice));
     }
   }
-  HIP_NEW(hipMalloc(&s->S, sizeof(double) * n * s->nfields));
-  HIP_NEW(hipMalloc(&s->flags, sizeof(uint32_t) * n));
-  HIP_NEW(hipMalloc(&s->conv, sizeof(int32_t) * n));
-  if (int rc = stage_create(s)) return cleanup(rc, g_err);
-  HIP_NEW(hipMemsetAsync(s->S, 0, sizeof(double) * n * s->nfields, s->stream));
-  HIP_NEW(hipMemsetAsync(s->conv, 0, sizeof(int32_t) * n, s->stream));
+  HIP_TRY(hipMalloc(s->S.out(), sizeof(double) * n * s->nfields));
+  HIP_TRY(hipMalloc(s->flags.out(), sizeof(uint32_t) * n));
+  HIP_TRY(hipMalloc(s->conv.out(), sizeof(int32_t) * n));
+  if (int rc = stage_create(s)) return rc;
+  HIP_TRY(hipMemsetAsync(s->S.get(), 0, sizeof(double) * n * s->nfields, s->stream));
+  HIP_TRY(hipMemsetAsync(s->conv.get(), 0, sizeof(int32_t) * n, s->stream));
   // Sim::converged starts true (reference src/sim/sim.h:70); SimRobotState.ik_success starts true
   {
     std::vector<uint32_t> f(n, kConverged | kIkSuccess);
-    HIP_NEW(hipMemcpyAsync(s->flags, f.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s->stream));
-    HIP_NEW(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpyAsync(s->flags.get(), f.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
   }
   // mjData starts at qpos0
   {
     std::vector<double> q0 = tile(s->dm.qpos0, s->nl, n_envs);
     int rc = scatter_host(s, field_of(s, "qpos"), s->nl, q0.data(), nullptr);
     if (!rc) rc = scatter_host(s, field_of(s, "qpre"), s->nl, q0.data(), nullptr);
-    if (rc) return cleanup(rc, g_err);
+    if (rc) return rc;
   }
-  if (upload_model(s)) return cleanup(RCSH_ERR_DEVICE, g_err);
+  if (int rc = upload_model(s)) return rc;
   if (const char* cc = std::getenv("RCSH_CONTACT_CHECK")) s->contact_check = std::atoi(cc) != 0;
   if (const char* rf = std::getenv("RCSH_RENDER_F64")) s->render_f64 = std::atoi(rf) != 0;
-  if (upload_contact_table(s)) return cleanup(RCSH_ERR_DEVICE, g_err);  // (the contact check's pair tables exist before any robot is attached)
-#undef HIP_NEW
-  *out = s;
+  if (int rc = upload_contact_table(s)) return rc;  // (the contact check's pair tables exist before any robot is attached)
+  *out = owner.release();
   return RCSH_OK;
 }
 
+// What has an order is written out; the rest is the handle's members, destroyed in reverse (own_stream last).
 void rcsh_sim_destroy(rcsh_sim* s) {
   if (!s) return;
   hipSetDevice(s->device);
   if (s->stream) hipStreamSynchronize(s->stream);
-  if (s->comm || s->copy) rcsh_comm_destroy(s);
-  for (auto e : s->ev_start) hipEventDestroy(e);
-  if (s->order_ev) hipEventDestroy(s->order_ev);
-  for (auto e : s->ev_stop) hipEventDestroy(e);
-  hipFree(s->d_model); hipFree(s->d_coll_xyzr); hipFree(s->d_coll_cls); hipFree(s->S); hipFree(s->flags); hipFree(s->conv);
-  hipFree(s->d_cgeoms); hipFree(s->d_cverts); hipFree(s->d_pairs.p); hipFree(s->d_chk_geoms.p); hipFree(s->d_chk_ent.p); hipFree(s->d_lev);
-  hipFree(s->d_slack);
-  hipFree(s->d_query.p);
-  hipFree(s->d_guard);
-  if (s->h_guard) hipHostFree(s->h_guard);
-  hipFree(s->d_episode);
-  if (s->h_episode) hipHostFree(s->h_episode);
-  hipFree(s->d_esc); hipFree(s->d_esc_ctr); hipFree(s->d_snap); hipFree(s->d_snap_flags); hipFree(s->d_snap_conv);
-  hipFree(s->rend.last); hipFree(s->rend.snap); hipFree(s->rend.count);
-  hipFree(s->d_boxtask); hipFree(s->d_rshapes); hipFree(s->d_rplanes); hipFree(s->d_rcolours); hipFree(s->d_frames); hipFree(s->d_wframes); hipFree(s->d_image.p);
-  hipFree(s->d_redge_planes); hipFree(s->d_redge_verts); hipFree(s->d_rviews);
-  if (s->h_pin.p) hipHostFree(s->h_pin.p);
-  hipFree(s->stage.base);
-  if (s->own_stream) hipStreamDestroy(s->own_stream);
+  rcsh_comm_destroy(s);
   delete s;
 }
 
@@ -825,7 +820,7 @@ void* rcsh_sim_stream(rcsh_sim* s) { return s ? (void*)s->stream : nullptr; }
 int rcsh_sim_set_stream(rcsh_sim* s, void* hip_stream) {
   REQUIRE_SIM(s);
   HIP_TRY(hipStreamSynchronize(s->stream));
-  s->stream = hip_stream ? (hipStream_t)hip_stream : s->own_stream;
+  s->stream = hip_stream ? (hipStream_t)hip_stream : s->own_stream.get();
   return RCSH_OK;
 }
 
@@ -834,9 +829,9 @@ int rcsh_sim_wait_for(rcsh_sim* s, rcsh_sim* producer) {
   if (!producer) return fail(RCSH_ERR_ARG, "null producer handle");
   if (producer == s || producer->stream == s->stream) return RCSH_OK;  // same stream: already ordered
   HIP_TRY(hipSetDevice(producer->device));
-  if (!producer->order_ev) HIP_TRY(hipEventCreateWithFlags(&producer->order_ev, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(producer->order_ev, producer->stream));
-  HIP_TRY(hipStreamWaitEvent(s->stream, producer->order_ev, 0));
+  if (!producer->order_ev) HIP_TRY(hipEventCreateWithFlags(producer->order_ev.out(), hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(producer->order_ev.get(), producer->stream));
+  HIP_TRY(hipStreamWaitEvent(s->stream, producer->order_ev.get(), 0));
   return RCSH_OK;
 }
 
@@ -895,7 +890,7 @@ int rcsh_sim_is_converged(rcsh_sim* s, uint8_t* converged, int32_t* steps) {
   int rc = flag_host(s, kConverged, converged);
   if (rc) return rc;
   if (steps) {
-    HIP_TRY(hipMemcpyAsync(steps, s->conv, sizeof(int32_t) * s->n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(steps, s->conv.get(), sizeof(int32_t) * s->n, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
   return RCSH_OK;
@@ -916,20 +911,20 @@ int rcsh_sim_reset(rcsh_sim* s, const uint8_t* mask) {
   if (!rc) rc = scatter_host(s, field_of(s, "xs"), s->nl, z.data(), mask);  // (mj_resetData: qacc_warmstart := 0)
   if (!rc) rc = flags_update_host(s, 0, kContactOverflow | kContactUnresolved | kContactResolved | kEscQuiet, mask);
   if (!rc) rc = scatter_host(s, field_of(s, "sep"), kCheckSep, z.data(), mask);
-  if (!rc && s->d_esc) {
+  if (!rc && s->esc.mask) {
     // per-environment escalation: a reset environment starts over on the lean kernel
     const size_t nw = ((size_t)s->n + 63) / 64;
     std::vector<uint64_t> w(3 * nw, 0);
     if (mask) {
-      HIP_TRY(hipMemcpyAsync(w.data(), s->d_esc, sizeof(uint64_t) * nw, hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(hipMemcpyAsync(w.data(), s->esc.mask.get(), sizeof(uint64_t) * nw, hipMemcpyDeviceToHost, s->stream));
       HIP_TRY(hipStreamSynchronize(s->stream));
       for (int e = 0; e < s->n; ++e)
         if (mask[e]) w[e >> 6] &= ~(1ull << (e & 63));
     }
-    HIP_TRY(hipMemcpyAsync(s->d_esc, w.data(), sizeof(uint64_t) * 3 * nw, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->esc.mask.get(), w.data(), sizeof(uint64_t) * 3 * nw, hipMemcpyHostToDevice, s->stream));
     uint32_t ctr[4] = {0, 0, 0, 0};  // (RunOp::esc_ctr: [1] has to say how many are escalated -- a role-2 launch trusts a zero)
     for (size_t i = 0; i < nw; ++i) ctr[1] += (uint32_t)__builtin_popcountll(w[i]);
-    HIP_TRY(hipMemcpyAsync(s->d_esc_ctr, ctr, sizeof(ctr), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->esc.ctr.get(), ctr, sizeof(ctr), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
   if (!rc && s->box.present) {
@@ -1162,12 +1157,12 @@ int query_finite(const double* a, size_t n, const char* what) {
 QueryArgs query_args(rcsh_sim* s, int32_t m, int32_t kinds) {
   const Params P = make_params(s);
   QueryArgs A{};
-  A.links = reinterpret_cast<const LinkRec*>(reinterpret_cast<const char*>(s->d_model) + sizeof(DevModel));
+  A.links = reinterpret_cast<const LinkRec*>(reinterpret_cast<const char*>(s->d_model.get()) + sizeof(DevModel));
   A.ck = P.chk;
   A.ck.slack = nullptr;
   A.ck.pad = 0;
-  A.geoms = s->d_cgeoms;
-  A.verts = s->d_cverts;
+  A.geoms = s->d_cgeoms.get();
+  A.verts = s->d_cverts.get();
   for (int k = 0; k < 3; ++k) A.plane_n[k] = s->cp.plane_n[k];
   A.plane_d = s->cp.plane_d;
   A.has_plane = s->cp.has_plane ? 1 : 0;
@@ -1245,7 +1240,7 @@ int rcsh_collision_query(rcsh_sim* s, const double* q, const double* free_qpos, 
   if (free_qpos && (rc = query_finite(free_qpos, n * 7, "free_qpos"))) return rc;
   const size_t oq = 0, of = oq + 8 * n * nl, oh = of + (free_qpos ? 8 * n * 7 : 0), ok = align8(oh + n), op = align8(ok + n), end = op + 8 * n;
   if ((rc = grow_device(s, s->d_query, end))) return rc;
-  char* d = static_cast<char*>(s->d_query.p);
+  char* d = static_cast<char*>(s->d_query.p.get());
   HIP_TRY(hipMemcpyAsync(d + oq, q, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
   if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
   rc = point_query_dev(s, reinterpret_cast<const double*>(d + oq), free_qpos ? reinterpret_cast<const double*>(d + of) : nullptr, m, kinds,
@@ -1279,7 +1274,7 @@ int rcsh_motion_query(rcsh_sim* s, const double* q_from, const double* q_to, con
   if (free_qpos && (rc = query_finite(free_qpos, n * 7, "free_qpos"))) return rc;
   const size_t oa = 0, ob = oa + 8 * n * nl, of = ob + 8 * n * nl, orr = of + (free_qpos ? 8 * n * 7 : 0), ot = orr + 8 * n, end = ot + 8 * n;
   if ((rc = grow_device(s, s->d_query, end))) return rc;
-  char* d = static_cast<char*>(s->d_query.p);
+  char* d = static_cast<char*>(s->d_query.p.get());
   HIP_TRY(hipMemcpyAsync(d + oa, q_from, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipMemcpyAsync(d + ob, q_to, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
   if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
@@ -1488,14 +1483,14 @@ int rcsh_sim_set_contact_options(rcsh_sim* s, const rcsh_contact_options* o) {
   // (whenever the option is switched -- off, on, or between its forms -- the escalation masks, their counters and the phantom box's warm
   // start begin empty: stale bits of a rollout under another option would send environments to a launch that no longer knows them;
   // advisor, round 5)
-  if (s->d_esc) {
+  if (s->esc.mask) {
     const size_t nw = ((size_t)s->n + 63) / 64;
-    HIP_TRY(hipMemsetAsync(s->d_esc, 0, sizeof(uint64_t) * 3 * nw, s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_esc_ctr, 0, sizeof(uint32_t) * 4, s->stream));
+    HIP_TRY(hipMemsetAsync(s->esc.mask.get(), 0, sizeof(uint64_t) * 3 * nw, s->stream));
+    HIP_TRY(hipMemsetAsync(s->esc.ctr.get(), 0, sizeof(uint32_t) * 4, s->stream));
     int f_box = -1;
     dispatch_topology(s->narm, s->grip, [&](auto topo) { f_box = (int)Lay<decltype(topo)>::BOX; });
-    if (f_box >= 0) HIP_TRY(hipMemsetAsync(s->S + (size_t)(f_box + kBoxX) * s->n, 0, sizeof(double) * (size_t)(kBoxState - kBoxX) * s->n, s->stream));
-    if (s->d_slack) HIP_TRY(hipMemsetAsync(s->d_slack, 0, sizeof(float) * (size_t)kSlackStride * s->n, s->stream));
+    if (f_box >= 0) HIP_TRY(hipMemsetAsync(s->S.get() + (size_t)(f_box + kBoxX) * s->n, 0, sizeof(double) * (size_t)(kBoxState - kBoxX) * s->n, s->stream));
+    if (int rc = void_remembered_gaps(s)) return rc;
   }
   if (!o->resolve_robot_contacts) { s->box = BoxCfg{}; s->esc_mode = false; return RCSH_OK; }
   if (!(s->narm == 7 && s->grip && !s->dm.has_friction)) return fail(RCSH_ERR_MODEL, "contacts of the robot's geoms are resolved for the FR3 + hand archetype (no dry joint friction)");
@@ -1507,22 +1502,25 @@ int rcsh_sim_set_contact_options(rcsh_sim* s, const rcsh_contact_options* o) {
   BoxCfg b{};
   b.present = 0;
   b.resolve = 1 | (o->resolve_robot_contacts & 2);  // (bit 1: contacts between two geoms of the robot too)
-  s->esc_mode = (o->resolve_robot_contacts & 4) != 0;  // (bit 2: environment by environment instead of the whole batch)
-  if (s->esc_mode && !s->d_esc) {
+  const bool esc_mode = (o->resolve_robot_contacts & 4) != 0;  // (bit 2: environment by environment instead of the whole batch)
+  // what the option needs and the handle does not have yet is built here and attached below, with the option itself: the five
+  // escalation buffers as one group, the slack record as another
+  rcsh_sim::EscBufs esc;
+  DevBuf<float> slack;
+  if (esc_mode && !s->esc.mask) {
     const size_t nw = ((size_t)s->n + 63) / 64;
-    HIP_TRY(hipMalloc(&s->d_esc, sizeof(uint64_t) * 3 * nw));
-    HIP_TRY(hipMalloc(&s->d_esc_ctr, sizeof(uint32_t) * 4));
-    HIP_TRY(hipMalloc(&s->d_snap, sizeof(double) * (size_t)(s->nfields + kMaxRateCams) * s->n));  // (+ the rate-driven cameras' clocks)
-    HIP_TRY(hipMalloc(&s->d_snap_flags, sizeof(uint32_t) * s->n));
-    HIP_TRY(hipMalloc(&s->d_snap_conv, sizeof(int32_t) * s->n));
-    if (const char* e = std::getenv("RCSH_CONV_CHUNK")) s->conv_chunk = std::atoi(e);
-    HIP_TRY(hipMemsetAsync(s->d_esc, 0, sizeof(uint64_t) * 3 * nw, s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_esc_ctr, 0, sizeof(uint32_t) * 4, s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_snap, 0, sizeof(double) * (size_t)(s->nfields + kMaxRateCams) * s->n, s->stream));
+    HIP_TRY(hipMalloc(esc.mask.out(), sizeof(uint64_t) * 3 * nw));
+    HIP_TRY(hipMalloc(esc.ctr.out(), sizeof(uint32_t) * 4));
+    HIP_TRY(hipMalloc(esc.snap.out(), sizeof(double) * (size_t)(s->nfields + kMaxRateCams) * s->n));  // (+ the rate-driven cameras' clocks)
+    HIP_TRY(hipMalloc(esc.snap_flags.out(), sizeof(uint32_t) * s->n));
+    HIP_TRY(hipMalloc(esc.snap_conv.out(), sizeof(int32_t) * s->n));
+    HIP_TRY(hipMemsetAsync(esc.mask.get(), 0, sizeof(uint64_t) * 3 * nw, s->stream));
+    HIP_TRY(hipMemsetAsync(esc.ctr.get(), 0, sizeof(uint32_t) * 4, s->stream));
+    HIP_TRY(hipMemsetAsync(esc.snap.get(), 0, sizeof(double) * (size_t)(s->nfields + kMaxRateCams) * s->n, s->stream));
   }
   if ((b.resolve & 2) && !s->d_slack) {
-    HIP_TRY(hipMalloc(&s->d_slack, sizeof(float) * (size_t)kSlackStride * s->n));
-    HIP_TRY(hipMemsetAsync(s->d_slack, 0, sizeof(float) * (size_t)kSlackStride * s->n, s->stream));  // (no gap known: every pair is looked at)
+    HIP_TRY(hipMalloc(slack.out(), sizeof(float) * (size_t)kSlackStride * s->n));
+    HIP_TRY(hipMemsetAsync(slack.get(), 0, sizeof(float) * (size_t)kSlackStride * s->n, s->stream));  // (no gap known: every pair is looked at)
   }
   b.noslip_iterations = o->noslip_iterations;
   b.qpos0[2] = 1000.0; b.qpos0[3] = 1.0;
@@ -1535,6 +1533,13 @@ int rcsh_sim_set_contact_options(rcsh_sim* s, const rcsh_contact_options* o) {
   b.plane_z = s->cp.plane_d;
   b.scale = 1.0 / (s->dm.inertia_diag_sum / s->nl * s->nl);  // 1 / (meaninertia * nv)
   b.noslip_tolerance = o->noslip_tolerance;
+  // the last allocation is behind: the option and its buffers are attached together (the two uploads below read them from the handle)
+  if (esc.mask) {
+    s->esc = std::move(esc);
+    if (const char* e = std::getenv("RCSH_CONV_CHUNK")) s->conv_chunk = std::atoi(e);
+  }
+  if (slack) s->d_slack = std::move(slack);
+  s->esc_mode = esc_mode;
   s->box = b;
   if (int rc = upload_boxtask(s)) return rc;
   return upload_contact_table(s);
@@ -1559,10 +1564,10 @@ int rcsh_sim_contact_escalated(rcsh_sim* s, uint8_t* now, uint8_t* ever) {
   REQUIRE_SIM(s);
   if (now) {
     std::memset(now, 0, s->n);
-    if (s->esc_mode && s->d_esc) {
+    if (s->esc_mode && s->esc.mask) {
       const size_t nw = ((size_t)s->n + 63) / 64;
       std::vector<uint64_t> w(nw);
-      HIP_TRY(hipMemcpyAsync(w.data(), s->d_esc, sizeof(uint64_t) * nw, hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(hipMemcpyAsync(w.data(), s->esc.mask.get(), sizeof(uint64_t) * nw, hipMemcpyDeviceToHost, s->stream));
       HIP_TRY(hipStreamSynchronize(s->stream));
       for (int e = 0; e < s->n; ++e) now[e] = (uint8_t)((w[e >> 6] >> (e & 63)) & 1u);
     }
@@ -1628,11 +1633,11 @@ int rcsh_sim_get_state(rcsh_sim* s, void* blob) {
     b += kStateHeader;
   }
   const size_t ns = sizeof(double) * (size_t)s->n * s->nfields, nf = sizeof(uint32_t) * (size_t)s->n, nc = sizeof(int32_t) * (size_t)s->n;
-  HIP_TRY(hipMemcpyAsync(b, s->S, ns, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(b + ns, s->flags, nf, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(b + ns + nf, s->conv, nc, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(b, s->S.get(), ns, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(b + ns, s->flags.get(), nf, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(b + ns + nf, s->conv.get(), nc, hipMemcpyDeviceToHost, s->stream));
   const size_t ne = sizeof(uint64_t) * (((size_t)s->n + 63) / 64);
-  if (s->d_esc) HIP_TRY(hipMemcpyAsync(b + ns + nf + nc, s->d_esc, ne, hipMemcpyDeviceToHost, s->stream));
+  if (s->esc.mask) HIP_TRY(hipMemcpyAsync(b + ns + nf + nc, s->esc.mask.get(), ne, hipMemcpyDeviceToHost, s->stream));
   else std::memset(b + ns + nf + nc, 0, ne);
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RCSH_OK;
@@ -1649,18 +1654,18 @@ int rcsh_sim_set_state(rcsh_sim* s, const void* blob) {
     b += kStateHeader;
   }
   const size_t ns = sizeof(double) * (size_t)s->n * s->nfields, nf = sizeof(uint32_t) * (size_t)s->n, nc = sizeof(int32_t) * (size_t)s->n;
-  if (s->d_slack) HIP_TRY(hipMemsetAsync(s->d_slack, 0, sizeof(float) * (size_t)kSlackStride * s->n, s->stream));  // (see scatter_host)
-  HIP_TRY(hipMemcpyAsync(s->S, b, ns, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(s->flags, b + ns, nf, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(s->conv, b + ns + nf, nc, hipMemcpyHostToDevice, s->stream));
-  if (s->d_esc) {
+  if (int rc = void_remembered_gaps(s)) return rc;
+  HIP_TRY(hipMemcpyAsync(s->S.get(), b, ns, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->flags.get(), b + ns, nf, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->conv.get(), b + ns + nf, nc, hipMemcpyHostToDevice, s->stream));
+  if (s->esc.mask) {
     const size_t ne = sizeof(uint64_t) * (((size_t)s->n + 63) / 64);
-    HIP_TRY(hipMemcpyAsync(s->d_esc, b + ns + nf + nc, ne, hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_esc + ne / sizeof(uint64_t), 0, 2 * ne, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->esc.mask.get(), b + ns + nf + nc, ne, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemsetAsync(s->esc.mask.get() + ne / sizeof(uint64_t), 0, 2 * ne, s->stream));
     uint32_t ctr[4] = {0, 0, 0, 0};  // (RunOp::esc_ctr[1]: how many are escalated)
     const uint64_t* w = reinterpret_cast<const uint64_t*>(b + ns + nf + nc);
     for (size_t i = 0; i < ne / sizeof(uint64_t); ++i) { uint64_t v; std::memcpy(&v, w + i, sizeof(v)); ctr[1] += (uint32_t)__builtin_popcountll(v); }
-    HIP_TRY(hipMemcpyAsync(s->d_esc_ctr, ctr, sizeof(ctr), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->esc.ctr.get(), ctr, sizeof(ctr), hipMemcpyHostToDevice, s->stream));
   }
   HIP_TRY(hipStreamSynchronize(s->stream));
   return RCSH_OK;
@@ -1705,7 +1710,7 @@ struct EpisodeRecord {
 };
 EpisodeRecord episode_record(const rcsh_sim* s) {
   const EpisodeLayout E = episode_layout(s);
-  char* d = static_cast<char*>(s->d_episode);
+  char* d = static_cast<char*>(s->d_episode.get());
   auto at = [&](size_t o, auto* type) { return reinterpret_cast<decltype(type)>(d + o); };
   EpisodeRecord r{};
   r.done = at(E.done, r.done); r.terminated = at(E.terminated, r.terminated); r.truncated = at(E.truncated, r.truncated);
@@ -1768,9 +1773,15 @@ int rcsh_env_configure_autoreset(rcsh_sim* s, const rcsh_autoreset_desc* a) {
   if (s->rend.ncam > 0)
     return fail(RCSH_ERR_STATE, "a render schedule is set: rate-driven cameras under autoreset are not built (remove it with rcsh_sim_set_render_schedule(ncam = 0) first)");
   const EpisodeLayout E = episode_layout(s);
-  if (!s->d_episode) HIP_TRY(hipMalloc(&s->d_episode, E.bytes));
-  if (!s->h_episode) { void* p = nullptr; HIP_TRY(hipHostMalloc(&p, E.host_bytes, hipHostMallocDefault)); s->h_episode = (char*)p; }
-  HIP_TRY(hipMemsetAsync(s->d_episode, 0, E.bytes, s->stream));  // every counter begins again
+  if (!s->d_episode) {  // the record and its page-locked copy: both or neither
+    DevBuf<void> d;
+    PinBuf<char> h;
+    HIP_TRY(hipMalloc(d.out(), E.bytes));
+    HIP_TRY(hipHostMalloc(h.out(), E.host_bytes, hipHostMallocDefault));
+    s->d_episode = std::move(d);
+    s->h_episode = std::move(h);
+  }
+  HIP_TRY(hipMemsetAsync(s->d_episode.get(), 0, E.bytes, s->stream));  // every counter begins again
   s->autoreset.configured = true;
   s->autoreset.enabled = a->enabled != 0;
   s->autoreset.desc = *a;
@@ -1800,7 +1811,7 @@ int rcsh_env_autoreset_last(rcsh_sim* s, uint8_t* done, uint8_t* terminated, uin
   if (!s->autoreset.configured || !s->episode_stepped) return fail(RCSH_ERR_STATE, "no step under autoreset has run");
   const size_t n = (size_t)s->n;
   const EpisodeLayout E = episode_layout(s);
-  const char* d = static_cast<const char*>(s->d_episode);
+  const char* d = static_cast<const char*>(s->d_episode.get());
   const struct { void* dst; size_t at, bytes; bool front; } pieces[] = {
       {episode_return, E.episode_return, 8 * n, true}, {episode_length, E.episode_length, 4 * n, true},
       {done, E.done, n, true}, {terminated, E.terminated, n, true}, {truncated, E.truncated, n, true}, {time_limit, E.time_limit, n, true},
@@ -1811,7 +1822,7 @@ int rcsh_env_autoreset_last(rcsh_sim* s, uint8_t* done, uint8_t* terminated, uin
   bool wait = false;
   for (const auto& p : pieces) {
     if (!p.dst) continue;
-    if (p.front && s->episode_host_valid) { std::memcpy(p.dst, s->h_episode + p.at, p.bytes); continue; }  // (rcsh_env_step brought it along)
+    if (p.front && s->episode_host_valid) { std::memcpy(p.dst, s->h_episode.get() + p.at, p.bytes); continue; }  // (rcsh_env_step brought it along)
     HIP_TRY(hipMemcpyAsync(p.dst, d + p.at, p.bytes, hipMemcpyDeviceToHost, s->stream));
     wait = true;
   }
@@ -1845,7 +1856,7 @@ namespace {
 struct GuardRecord { int32_t* result; double* t_contact; uint8_t* blocked; uint8_t* hold; };
 GuardRecord guard_record(const rcsh_sim* s, int which) {  // 0: the last guarded step, 1: the peek's scratch
   const GuardLayout G = guard_layout(s);
-  char* d = static_cast<char*>(s->d_guard) + (size_t)which * G.bytes;
+  char* d = static_cast<char*>(s->d_guard.get()) + (size_t)which * G.bytes;
   GuardRecord r{};
   r.t_contact = reinterpret_cast<double*>(d + G.t_contact);
   r.result = reinterpret_cast<int32_t*>(d + G.result);
@@ -1881,8 +1892,8 @@ int guard_launch(rcsh_sim* s, const double* action_dev, int32_t* result, double*
   constexpr double kGuardSlideTol = 5e-4;
   static_assert(kGuardSlideTol <= 0.5 * kLeverSlack, "the guard's slide tolerance lives inside the levers' additive slack");
   for (int L = 0; L < 12; ++L) { G.Q.slide_lo[L] -= kGuardSlideTol; G.Q.slide_hi[L] += kGuardSlideTol; }
-  G.S = s->S;
-  G.flags = s->flags;
+  G.S = s->S.get();
+  G.flags = s->flags.get();
   G.action = action_dev;
   G.env = s->env;
   G.box_field = box ? field_of(s, "box") + kBoxQ : -1;
@@ -1910,8 +1921,14 @@ int rcsh_env_configure_guard(rcsh_sim* s, const rcsh_guard_desc* g) {
     return fail(RCSH_ERR_STATE, "the collision guard guards joint-space actions only: the environments are configured for a Cartesian control mode");
   int rc = query_check(s, s->n, g->kinds, nullptr);
   if (rc) return rc;
-  if (!s->d_guard) HIP_TRY(hipMalloc(&s->d_guard, 2 * guard_layout(s).bytes));
-  if (!s->h_guard) { void* p = nullptr; HIP_TRY(hipHostMalloc(&p, guard_layout(s).host_bytes, hipHostMallocDefault)); s->h_guard = (char*)p; }
+  if (!s->d_guard) {  // the two records and the page-locked copy: both or neither
+    DevBuf<void> d;
+    PinBuf<char> h;
+    HIP_TRY(hipMalloc(d.out(), 2 * guard_layout(s).bytes));
+    HIP_TRY(hipHostMalloc(h.out(), guard_layout(s).host_bytes, hipHostMallocDefault));
+    s->d_guard = std::move(d);
+    s->h_guard = std::move(h);
+  }
   s->guard.configured = true;
   s->guard.enabled = g->enabled != 0;
   s->guard.kinds = g->kinds;
@@ -1938,7 +1955,7 @@ int rcsh_env_guard_peek(rcsh_sim* s, const double* action, int32_t* result, doub
   int rc = query_finite(action, na, "action");
   if (rc) return rc;
   if ((rc = grow_device(s, s->d_query, 8 * na))) return rc;
-  double* d_action = static_cast<double*>(s->d_query.p);
+  double* d_action = static_cast<double*>(s->d_query.p.get());
   const GuardRecord r = guard_record(s, 1);
   HIP_TRY(hipMemcpyAsync(d_action, action, 8 * na, hipMemcpyHostToDevice, s->stream));
   if ((rc = guard_launch(s, d_action, r.result, r.t_contact, r.blocked, nullptr))) return rc;
@@ -1965,7 +1982,7 @@ int rcsh_env_guard_last(rcsh_sim* s, int32_t* result, double* t_contact, uint8_t
   const size_t n = (size_t)s->n;
   if (s->guard_host_valid) {  // (rcsh_env_step brought the record along with its outputs)
     const GuardLayout G = guard_layout(s);
-    const char* hg = s->h_guard;
+    const char* hg = s->h_guard.get();
     if (t_contact) std::memcpy(t_contact, hg + G.t_contact, 8 * n);
     if (result) std::memcpy(result, hg + G.result, 4 * n);
     if (blocked) std::memcpy(blocked, hg + G.blocked, n);
@@ -2174,27 +2191,23 @@ int rcsh_sim_set_render_scene(rcsh_sim* s, const rcsh_render_scene_desc* d) {
       }
     }
   }
-  const bool first_scene = s->d_frames == nullptr;
-  hipFree(s->d_rshapes); hipFree(s->d_rplanes); hipFree(s->d_frames); hipFree(s->d_wframes); hipFree(s->d_rcolours);
-  hipFree(s->d_redge_planes); hipFree(s->d_redge_verts); hipFree(s->d_rviews);
-  s->d_rshapes = nullptr; s->d_rplanes = nullptr; s->d_frames = nullptr; s->d_wframes = nullptr; s->d_rcolours = nullptr;
-  s->d_redge_planes = nullptr; s->d_redge_verts = nullptr; s->d_rviews = nullptr;
-  s->rscene.colours = nullptr;
-  s->rscene.edge_planes = nullptr; s->rscene.edge_verts = nullptr; s->rscene.views = nullptr; s->rscene.view_stride = 0;
+  // the new scene is built beside the old one, which stays attached and valid until the new one is complete
+  const bool first_scene = !s->rbuf.frames;
+  rcsh_sim::RenderBufs nb;  // (without colours: rcsh_sim_set_render_colours follows a new scene)
   const int np = d->nplanes > 0 ? d->nplanes : 1;
-  HIP_TRY(hipMalloc(&s->d_rshapes, sizeof(RenderShape) * d->nshape));
-  HIP_TRY(hipMalloc(&s->d_rplanes, sizeof(double) * 4 * np));
-  HIP_TRY(hipMalloc(&s->d_frames, sizeof(double) * 12 * (size_t)(s->nl + 1) * s->n));
-  HIP_TRY(hipMalloc(&s->d_wframes, sizeof(double) * kShapeFrameDoubles * (size_t)(d->nshape + 1) * s->n));
+  HIP_TRY(hipMalloc(nb.shapes.out(), sizeof(RenderShape) * d->nshape));
+  HIP_TRY(hipMalloc(nb.planes.out(), sizeof(double) * 4 * np));
+  HIP_TRY(hipMalloc(nb.frames.out(), sizeof(double) * 12 * (size_t)(s->nl + 1) * s->n));
+  HIP_TRY(hipMalloc(nb.wframes.out(), sizeof(double) * kShapeFrameDoubles * (size_t)(d->nshape + 1) * s->n));
   if (view_stride > 0) {
-    HIP_TRY(hipMalloc(&s->d_redge_planes, sizeof(int32_t) * edge_planes.size()));
-    HIP_TRY(hipMalloc(&s->d_redge_verts, sizeof(double) * edge_verts.size()));
-    HIP_TRY(hipMalloc(&s->d_rviews, sizeof(double) * (size_t)view_stride * s->n));
-    HIP_TRY(hipMemcpyAsync(s->d_redge_planes, edge_planes.data(), sizeof(int32_t) * edge_planes.size(), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->d_redge_verts, edge_verts.data(), sizeof(double) * edge_verts.size(), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMalloc(nb.edge_planes.out(), sizeof(int32_t) * edge_planes.size()));
+    HIP_TRY(hipMalloc(nb.edge_verts.out(), sizeof(double) * edge_verts.size()));
+    HIP_TRY(hipMalloc(nb.views.out(), sizeof(double) * (size_t)view_stride * s->n));
+    HIP_TRY(hipMemcpyAsync(nb.edge_planes.get(), edge_planes.data(), sizeof(int32_t) * edge_planes.size(), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(nb.edge_verts.get(), edge_verts.data(), sizeof(double) * edge_verts.size(), hipMemcpyHostToDevice, s->stream));
   }
-  HIP_TRY(hipMemcpyAsync(s->d_rshapes, sh.data(), sizeof(RenderShape) * d->nshape, hipMemcpyHostToDevice, s->stream));
-  if (d->nplanes > 0) HIP_TRY(hipMemcpyAsync(s->d_rplanes, d->planes, sizeof(double) * 4 * d->nplanes, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(nb.shapes.get(), sh.data(), sizeof(RenderShape) * d->nshape, hipMemcpyHostToDevice, s->stream));
+  if (d->nplanes > 0) HIP_TRY(hipMemcpyAsync(nb.planes.get(), d->planes, sizeof(double) * 4 * d->nplanes, hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   // The kernels keep "the qpos the last position stage saw" (what mjData.xpos / geom_xpos derive from) only while a render
   // scene is attached.  A scene attached after some stepping starts from the current qpos instead of whatever the field held:
@@ -2202,17 +2215,18 @@ int rcsh_sim_set_render_scene(rcsh_sim* s, const rcsh_render_scene_desc* d) {
   if (first_scene) with_layout(s, [&](auto topo) {
     using L = Lay<decltype(topo)>;
     const size_t n = (size_t)s->n;
-    (void)hipMemcpyAsync(s->S + (size_t)L::QPRE * n, s->S + (size_t)L::QPOS * n, sizeof(double) * n * s->nl, hipMemcpyDeviceToDevice, s->stream);
+    (void)hipMemcpyAsync(s->S.get() + (size_t)L::QPRE * n, s->S.get() + (size_t)L::QPOS * n, sizeof(double) * n * s->nl, hipMemcpyDeviceToDevice, s->stream);
     if (s->box.present)
-      (void)hipMemcpyAsync(s->S + (size_t)(L::BOX + kBoxPre) * n, s->S + (size_t)(L::BOX + kBoxQ) * n, sizeof(double) * n * 7, hipMemcpyDeviceToDevice, s->stream);
+      (void)hipMemcpyAsync(s->S.get() + (size_t)(L::BOX + kBoxPre) * n, s->S.get() + (size_t)(L::BOX + kBoxQ) * n, sizeof(double) * n * 7, hipMemcpyDeviceToDevice, s->stream);
     return 0;
   });
   HIP_TRY(hipStreamSynchronize(s->stream));
+  s->rbuf = std::move(nb);  // (the old scene's buffers go here)
   s->rscene.nshape = d->nshape; s->rscene.nframes = s->nl + 1;
   s->rscene.znear = d->znear; s->rscene.zfar = d->zfar;
   s->rscene.inv_near = 1.0 / d->znear; s->rscene.inv_span = 1.0 / (1.0 / d->znear - 1.0 / d->zfar);
-  s->rscene.shapes = s->d_rshapes; s->rscene.planes = s->d_rplanes;
-  s->rscene.edge_planes = s->d_redge_planes; s->rscene.edge_verts = s->d_redge_verts; s->rscene.views = s->d_rviews; s->rscene.view_stride = view_stride;
+  s->rscene.shapes = s->rbuf.shapes.get(); s->rscene.planes = s->rbuf.planes.get(); s->rscene.colours = s->rbuf.colours.get();
+  s->rscene.edge_planes = s->rbuf.edge_planes.get(); s->rscene.edge_verts = s->rbuf.edge_verts.get(); s->rscene.views = s->rbuf.views.get(); s->rscene.view_stride = view_stride;
   return RCSH_OK;
 }
 
@@ -2250,7 +2264,7 @@ int rcsh_sim_add_camera(rcsh_sim* s, const rcsh_camera_desc* c, int32_t* cam_id)
 
 int rcsh_sim_set_render_colours(rcsh_sim* s, const rcsh_render_colours* c) {
   REQUIRE_SIM(s);
-  if (!s->d_frames) return fail(RCSH_ERR_STATE, "no render scene: call rcsh_sim_set_render_scene first");
+  if (!s->rbuf.frames) return fail(RCSH_ERR_STATE, "no render scene: call rcsh_sim_set_render_scene first");
   if (!c || !c->colour) return fail(RCSH_ERR_ARG, "null colour table");
   const int ns = s->rscene.nshape;
   std::vector<RenderColour> col(ns);
@@ -2260,10 +2274,10 @@ int rcsh_sim_set_render_colours(rcsh_sim* s, const rcsh_render_colours* c) {
     col[i].square = w[6]; col[i].checker = w[7];
     if (col[i].checker != 0.0 && !(col[i].square > 0)) return fail(RCSH_ERR_ARG, "render colours: checker squares need a positive edge length");
   }
-  if (!s->d_rcolours) HIP_TRY(hipMalloc(&s->d_rcolours, sizeof(RenderColour) * ns));
-  HIP_TRY(hipMemcpyAsync(s->d_rcolours, col.data(), sizeof(RenderColour) * ns, hipMemcpyHostToDevice, s->stream));
+  if (!s->rbuf.colours) HIP_TRY(hipMalloc(s->rbuf.colours.out(), sizeof(RenderColour) * ns));
+  HIP_TRY(hipMemcpyAsync(s->rbuf.colours.get(), col.data(), sizeof(RenderColour) * ns, hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
-  s->rscene.colours = s->d_rcolours;
+  s->rscene.colours = s->rbuf.colours.get();
   RenderShade& L = s->rscene.shade;
   for (int k = 0; k < 3; ++k) {
     L.ambient[k] = c->headlight_ambient[k]; L.head_diffuse[k] = c->headlight_diffuse[k];
@@ -2277,7 +2291,7 @@ int rcsh_sim_set_render_colours(rcsh_sim* s, const rcsh_render_colours* c) {
 
 int rcsh_sim_set_render_schedule(rcsh_sim* s, const int32_t* cam_ids, const double* seconds_between_calls, int32_t ncam, int32_t capacity) {
   REQUIRE_SIM(s);
-  if (!s->d_frames) return fail(RCSH_ERR_STATE, "no render scene: call rcsh_sim_set_render_scene first");
+  if (!s->rbuf.frames) return fail(RCSH_ERR_STATE, "no render scene: call rcsh_sim_set_render_scene first");
   if (ncam < 0 || ncam > kMaxRateCams) return fail(RCSH_ERR_ARG, "render schedule: at most 4 cameras with a frame rate");
   if (ncam > 0 && (!cam_ids || !seconds_between_calls || capacity < 1 || capacity > 256)) return fail(RCSH_ERR_ARG, "render schedule: bad arguments");
   if (ncam > 0 && s->autoreset.enabled)
@@ -2295,33 +2309,39 @@ int rcsh_sim_set_render_schedule(rcsh_sim* s, const int32_t* cam_ids, const doub
   for (int c = 0; same && c < ncam; ++c) same = s->rend_cam_id[c] == cam_ids[c] && s->rend.period[c] == seconds_between_calls[c];
   if (same) {
     if (capacity == s->rend.capacity) return RCSH_OK;
-    double* snap = nullptr;
-    HIP_TRY(hipMalloc(&snap, sizeof(double) * (size_t)capacity * nf * n));
-    HIP_TRY(hipMemcpy(snap, s->rend.snap, sizeof(double) * (size_t)s->rend.capacity * nf * n, hipMemcpyDeviceToDevice));
-    hipFree(s->rend.snap);
-    s->rend.snap = snap;
+    DevBuf<double> snap;
+    HIP_TRY(hipMalloc(snap.out(), sizeof(double) * (size_t)capacity * nf * n));
+    HIP_TRY(hipMemcpy(snap.get(), s->rend.snap, sizeof(double) * (size_t)s->rend.capacity * nf * n, hipMemcpyDeviceToDevice));
+    s->rend_snap = std::move(snap);
+    s->rend.snap = s->rend_snap.get();
     s->rend.capacity = capacity;
     return RCSH_OK;
   }
-  hipFree(s->rend.last); hipFree(s->rend.snap); hipFree(s->rend.count);
-  s->rend = RendCfg{};
-  s->rend_dropped = 0;
-  if (ncam == 0) return RCSH_OK;
-  HIP_TRY(hipMalloc(&s->rend.last, sizeof(double) * kMaxRateCams * n));
-  HIP_TRY(hipMalloc(&s->rend.snap, sizeof(double) * (size_t)capacity * nf * n));
-  HIP_TRY(hipMalloc(&s->rend.count, sizeof(int32_t) * n));
-  HIP_TRY(hipMemsetAsync(s->rend.count, 0, sizeof(int32_t) * n, s->stream));
-  // register_rendering_callback (sim.cpp:160-173): last_call_timestamp = -1 / frame_rate, "so that we will directly render"
-  std::vector<double> last(kMaxRateCams * n, 0.0);
-  for (int c = 0; c < ncam; ++c) {
-    s->rend.period[c] = seconds_between_calls[c];
-    s->rend_cam_id[c] = cam_ids[c];
-    for (size_t e = 0; e < n; ++e) last[c * n + e] = -seconds_between_calls[c];
+  // another schedule, or none: the new one is built in locals, the old one stays until it is complete
+  DevBuf<double> last_dev, snap;
+  DevBuf<int32_t> count;
+  RendCfg rend{};
+  if (ncam > 0) {
+    HIP_TRY(hipMalloc(last_dev.out(), sizeof(double) * kMaxRateCams * n));
+    HIP_TRY(hipMalloc(snap.out(), sizeof(double) * (size_t)capacity * nf * n));
+    HIP_TRY(hipMalloc(count.out(), sizeof(int32_t) * n));
+    HIP_TRY(hipMemsetAsync(count.get(), 0, sizeof(int32_t) * n, s->stream));
+    // register_rendering_callback (sim.cpp:160-173): last_call_timestamp = -1 / frame_rate, "so that we will directly render"
+    std::vector<double> last(kMaxRateCams * n, 0.0);
+    for (int c = 0; c < ncam; ++c) {
+      rend.period[c] = seconds_between_calls[c];
+      for (size_t e = 0; e < n; ++e) last[c * n + e] = -seconds_between_calls[c];
+    }
+    HIP_TRY(hipMemcpyAsync(last_dev.get(), last.data(), sizeof(double) * last.size(), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    rend.ncam = ncam;
+    rend.capacity = capacity;
   }
-  HIP_TRY(hipMemcpyAsync(s->rend.last, last.data(), sizeof(double) * last.size(), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  s->rend.ncam = ncam;
-  s->rend.capacity = capacity;
+  s->rend_last = std::move(last_dev); s->rend_snap = std::move(snap); s->rend_count = std::move(count);
+  rend.last = s->rend_last.get(); rend.snap = s->rend_snap.get(); rend.count = s->rend_count.get();
+  s->rend = rend;
+  for (int c = 0; c < ncam; ++c) s->rend_cam_id[c] = cam_ids[c];
+  s->rend_dropped = 0;
   return RCSH_OK;
 }
 
@@ -2385,7 +2405,7 @@ int rcsh_camera_render_snapshot(rcsh_sim* s, int32_t cam_id, int32_t slot, uint8
 
 int rcsh_camera_render_rgb_dev(rcsh_sim* s, int32_t cam_id, uint8_t* rgb, float* depth_gl, uint16_t* depth_mm, double* cam_pose) {
   REQUIRE_SIM(s);
-  if (!s->d_frames) return fail(RCSH_ERR_STATE, "no render scene: call rcsh_sim_set_render_scene first");
+  if (!s->rbuf.frames) return fail(RCSH_ERR_STATE, "no render scene: call rcsh_sim_set_render_scene first");
   if (rgb && !s->rscene.colours) return fail(RCSH_ERR_STATE, "no colours: call rcsh_sim_set_render_colours first");
   if (cam_id < 0 || cam_id >= (int)s->cams.size()) return fail(RCSH_ERR_ARG, "unknown camera id");
   const RenderCam& cam = s->cams[cam_id];
@@ -2393,27 +2413,27 @@ int rcsh_camera_render_rgb_dev(rcsh_sim* s, int32_t cam_id, uint8_t* rgb, float*
   bool ok = dispatch_topology(s->narm, s->grip, [&](auto topo) {
     using T = decltype(topo);
     if (s->frames_src)  // a record of the render schedule: qpre at field 0, the box's pre-step pose behind it
-      hipLaunchKernelGGL((k_link_frames<T>), dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->d_model, s->frames_src, s->n, 0,
-                         T::NL - kBoxPre, (int)s->box.present, s->d_frames);
+      hipLaunchKernelGGL((k_link_frames<T>), dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->d_model.get(), s->frames_src, s->n, 0,
+                         T::NL - kBoxPre, (int)s->box.present, s->rbuf.frames.get());
     else
-      hipLaunchKernelGGL((k_link_frames<T>), dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->d_model, s->S, s->n,
-                         (int)Lay<T>::QPRE, (int)Lay<T>::BOX, (int)s->box.present, s->d_frames);
+      hipLaunchKernelGGL((k_link_frames<T>), dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->d_model.get(), s->S.get(), s->n,
+                         (int)Lay<T>::QPRE, (int)Lay<T>::BOX, (int)s->box.present, s->rbuf.frames.get());
     err = hipGetLastError();
   });
   if (!ok) return fail(RCSH_ERR_MODEL, "no kernel instantiated for this archetype");
   if (err != hipSuccess) return fail(RCSH_ERR_DEVICE, std::string("k_link_frames launch: ") + hipGetErrorString(err));
-  hipLaunchKernelGGL(k_shape_frames, dim3(grid_for(s->n * (s->rscene.nshape + 1))), dim3(kBlock), 0, s->stream, s->rscene, cam, s->d_frames, s->n,
-                     s->d_wframes);
+  hipLaunchKernelGGL(k_shape_frames, dim3(grid_for(s->n * (s->rscene.nshape + 1))), dim3(kBlock), 0, s->stream, s->rscene, cam, s->rbuf.frames.get(), s->n,
+                     s->rbuf.wframes.get());
   // (the rays' arithmetic type: float unless rcsh_sim_set_render_f64 asked for the instantiation that equals the restatement bit for bit)
   const dim3 grid((unsigned)(((size_t)render_wgs_per_env(cam.width, cam.height) * (size_t)s->n + 7) / 8 * 8));  // (a multiple of 8: k_render_depth numbers its workgroups per XCD)
   auto cast = [&](auto zero) {
     using F = decltype(zero);
     if (s->rscene.views)
-      hipLaunchKernelGGL(k_hull_views<F>, dim3((unsigned)s->n * (unsigned)s->rscene.nshape), dim3(64), 0, s->stream, s->rscene, cam, s->d_wframes, s->n);
+      hipLaunchKernelGGL(k_hull_views<F>, dim3((unsigned)s->n * (unsigned)s->rscene.nshape), dim3(64), 0, s->stream, s->rscene, cam, s->rbuf.wframes.get(), s->n);
     if (rgb)
-      hipLaunchKernelGGL((k_render_depth<true, F>), grid, dim3(256), 0, s->stream, s->rscene, cam, s->d_wframes, s->n, depth_gl, depth_mm, cam_pose, rgb);
+      hipLaunchKernelGGL((k_render_depth<true, F>), grid, dim3(256), 0, s->stream, s->rscene, cam, s->rbuf.wframes.get(), s->n, depth_gl, depth_mm, cam_pose, rgb);
     else
-      hipLaunchKernelGGL((k_render_depth<false, F>), grid, dim3(256), 0, s->stream, s->rscene, cam, s->d_wframes, s->n, depth_gl, depth_mm, cam_pose,
+      hipLaunchKernelGGL((k_render_depth<false, F>), grid, dim3(256), 0, s->stream, s->rscene, cam, s->rbuf.wframes.get(), s->n, depth_gl, depth_mm, cam_pose,
                          (uint8_t*)nullptr);
   };
   if (s->render_f64) cast(0.0); else cast(0.0f);
@@ -2440,7 +2460,7 @@ int rcsh_camera_render_rgb(rcsh_sim* s, int32_t cam_id, uint8_t* rgb, float* dep
   const size_t off_mm = px * sizeof(float), off_pose = ((off_mm + px * sizeof(uint16_t) + 7) / 8) * 8, off_rgb = off_pose + sizeof(double) * 12 * s->n;
   const size_t need = off_rgb + 3 * px;
   if (int rc = grow_device(s, s->d_image, need)) return rc;
-  char* base = static_cast<char*>(s->d_image.p);
+  char* base = static_cast<char*>(s->d_image.p.get());
   float* dgl = reinterpret_cast<float*>(base);
   uint16_t* dmm = reinterpret_cast<uint16_t*>(base + off_mm);
   double* dpose = reinterpret_cast<double*>(base + off_pose);
@@ -2483,17 +2503,17 @@ static_assert(sizeof(CopyBlob) <= RCSH_COMM_COPY_BLOB_BYTES, "the blob fits what
 struct CopyCarrier {
   int rank = 0, world = 1;
   size_t bytes = 0;
-  void* recv[2] = {nullptr, nullptr};   // [world * bytes] each, this rank's
-  uint64_t* flags = nullptr;            // [2][2][kCopyMaxWorld], this rank's (fine-grained: peers write it, a waiting wavefront reads it)
-  void* peer_recv[kCopyMaxWorld][2] = {};
-  uint64_t* peer_flags[kCopyMaxWorld] = {};
+  DevBuf<void> recv[2];                 // [world * bytes] each, this rank's
+  DevBuf<uint64_t> flags;               // [2][2][kCopyMaxWorld], this rank's (fine-grained: peers write it, a waiting wavefront reads it)
+  void* peer_recv[kCopyMaxWorld][2] = {};     // views: the peers' receive buffers, IPC-mapped where opened[p] (closed by copy_carrier_free); the own rank's are recv
+  uint64_t* peer_flags[kCopyMaxWorld] = {};   // views: the peers' flag words, likewise
   bool opened[kCopyMaxWorld] = {};
-  hipStream_t cs[kCopyMaxWorld] = {};   // one copy stream per peer (own rank: the local block)
-  hipEvent_t cs_done[kCopyMaxWorld] = {}, acked = nullptr;
-  uint64_t* seq_ring = nullptr;         // pinned: the sequence numbers the flag copies read
+  Stream cs[kCopyMaxWorld];             // one copy stream per peer (own rank: the local block)
+  Event cs_done[kCopyMaxWorld], acked;
+  PinBuf<uint64_t> seq_ring;            // pinned: the sequence numbers the flag copies read
   uint64_t seq[2] = {0, 0};
   int ring_pos = 0;
-  uint32_t* timeout_flag = nullptr;     // pinned: a wait gave up (a peer died)
+  PinBuf<uint32_t> timeout_flag;        // pinned: a wait gave up (a peer died)
   bool connected = false;
   // how the flag words are written and waited for: stream memory operations (hipStreamWriteValue64 / hipStreamWaitValue64: the
   // command processor does both, nothing runs on a CU and nothing goes through a copy engine) with RCSH_COPY_CARRIER_FLAGS=value where
@@ -2503,10 +2523,10 @@ struct CopyCarrier {
   // wait for it and launches the graph -- four calls instead of ~5 W + 4.  The sequence number then lives on the device (qdev[slot],
   // bumped by the graph's first node); the flag words are 8-byte device-to-device copies of it, the waiting wavefronts read it.
   bool use_graph = true;
-  hipGraphExec_t gexec[2] = {nullptr, nullptr};
+  hipGraphExec_t gexec[2] = {nullptr, nullptr};  // (the graphs are destroyed by hand, first of all: copy_carrier_free)
   hipGraph_t graph[2] = {nullptr, nullptr};
-  const void* gsend[2] = {nullptr, nullptr};
-  uint64_t* qdev = nullptr;             // [2] the slots' sequence numbers (graph form)
+  const void* gsend[2] = {nullptr, nullptr};     // view: the caller's send buffer the slot's graph was captured for
+  DevBuf<uint64_t> qdev;                // [2] the slots' sequence numbers (graph form)
 };
 namespace {
 // one wavefront: waits until the `n` words at `w` (skipping index `skip`) have all reached `q`; gives up after ~20 s
@@ -2541,32 +2561,21 @@ __global__ void __launch_bounds__(64) k_wait_flags_at(const uint64_t* w, int n, 
   }
 }
 __global__ void k_bump(uint64_t* q) { *q += 1; }
-void copy_carrier_free(rcsh_sim* s) {
-  CopyCarrier* c = s->copy;
-  if (!c) return;
+// what has an order: the graphs, then the copy streams run dry, then the peers' mappings closed; the carrier's members do the rest
+void copy_carrier_free(CopyCarrier* c) {
   for (int k = 0; k < 2; ++k) {
     if (c->gexec[k]) hipGraphExecDestroy(c->gexec[k]);
     if (c->graph[k]) hipGraphDestroy(c->graph[k]);
   }
-  if (c->qdev) hipFree(c->qdev);
   for (int p = 0; p < c->world; ++p) {
-    if (c->cs[p]) hipStreamSynchronize(c->cs[p]);
+    if (c->cs[p]) hipStreamSynchronize(c->cs[p].get());
   }
   for (int p = 0; p < c->world; ++p) {
-    if (c->opened[p]) {
-      for (int k = 0; k < 2; ++k) if (c->peer_recv[p][k]) hipIpcCloseMemHandle(c->peer_recv[p][k]);
-      if (c->peer_flags[p]) hipIpcCloseMemHandle(c->peer_flags[p]);
-    }
-    if (c->cs[p]) hipStreamDestroy(c->cs[p]);
-    if (c->cs_done[p]) hipEventDestroy(c->cs_done[p]);
+    if (!c->opened[p]) continue;
+    for (int k = 0; k < 2; ++k) if (c->peer_recv[p][k]) hipIpcCloseMemHandle(c->peer_recv[p][k]);
+    if (c->peer_flags[p]) hipIpcCloseMemHandle(c->peer_flags[p]);
   }
-  if (c->acked) hipEventDestroy(c->acked);
-  for (int k = 0; k < 2; ++k) if (c->recv[k]) hipFree(c->recv[k]);
-  if (c->flags) hipFree(c->flags);
-  if (c->seq_ring) hipHostFree(c->seq_ring);
-  if (c->timeout_flag) hipHostFree(c->timeout_flag);
   delete c;
-  s->copy = nullptr;
 }
 }  // namespace
 
@@ -2574,31 +2583,28 @@ int rcsh_comm_copy_create(rcsh_sim* s, int32_t rank, int32_t world, size_t bytes
   REQUIRE_SIM(s);
   if (!blob || world < 1 || world > kCopyMaxWorld || rank < 0 || rank >= world || bytes_per_rank == 0 || bytes_per_rank % 8)
     return fail(RCSH_ERR_ARG, "copy carrier: need 0 <= rank < world <= 16 and a block size that is a multiple of 8 bytes");
-  if (s->comm || s->copy) return fail(RCSH_ERR_STATE, "a communicator is already attached to this sim");
+  if (s->comm.nccl || s->comm.copy) return fail(RCSH_ERR_STATE, "a communicator is already attached to this sim");
+  rcsh_sim::Comm cm;  // stream, events and carrier are built here and attached at the end: a failure leaves the handle without any
   CopyCarrier* c = new CopyCarrier;
-  s->copy = c;
+  cm.copy.reset(c);
   c->rank = rank; c->world = world; c->bytes = bytes_per_rank;
-  hipError_t he = hipSuccess;
-  auto ok = [&](hipError_t e) { if (he == hipSuccess) he = e; return he == hipSuccess; };
-  for (int k = 0; k < 2 && he == hipSuccess; ++k) ok(hipMalloc(&c->recv[k], bytes_per_rank * world));
+  for (int k = 0; k < 2; ++k) HIP_TRY(hipMalloc(c->recv[k].out(), bytes_per_rank * world));
   // (fine-grained: the words are written by copies other processes start and polled by a wavefront of this one)
-  void* fl = nullptr;
-  if (ok(hipExtMallocWithFlags(&fl, sizeof(uint64_t) * 2 * 2 * kCopyMaxWorld, hipDeviceMallocFinegrained))) {
-    c->flags = (uint64_t*)fl;
-    ok(hipMemset(c->flags, 0, sizeof(uint64_t) * 2 * 2 * kCopyMaxWorld));
-  }
-  if (he == hipSuccess && ok(hipMalloc((void**)&c->qdev, 2 * sizeof(uint64_t)))) ok(hipMemset(c->qdev, 0, 2 * sizeof(uint64_t)));
+  HIP_TRY(hipExtMallocWithFlags((void**)c->flags.out(), sizeof(uint64_t) * 2 * 2 * kCopyMaxWorld, hipDeviceMallocFinegrained));
+  HIP_TRY(hipMemset(c->flags.get(), 0, sizeof(uint64_t) * 2 * 2 * kCopyMaxWorld));
+  HIP_TRY(hipMalloc(c->qdev.out(), 2 * sizeof(uint64_t)));
+  HIP_TRY(hipMemset(c->qdev.get(), 0, 2 * sizeof(uint64_t)));
   if (const char* e = std::getenv("RCSH_COPY_CARRIER_GRAPH")) c->use_graph = std::atoi(e) != 0;
-  if (he == hipSuccess) ok(hipHostMalloc((void**)&c->seq_ring, sizeof(uint64_t) * kCopySeqRing, hipHostMallocDefault));
-  if (he == hipSuccess) ok(hipHostMalloc((void**)&c->timeout_flag, sizeof(uint32_t), hipHostMallocDefault));
-  if (he == hipSuccess) *c->timeout_flag = 0;
-  if (he == hipSuccess) ok(hipStreamCreateWithFlags(&s->comm_stream, hipStreamNonBlocking));
-  if (he == hipSuccess) ok(hipEventCreateWithFlags(&s->comm_ready, hipEventDisableTiming));
-  for (int k = 0; k < 2 && he == hipSuccess; ++k) ok(hipEventCreateWithFlags(&s->comm_done[k], hipEventDisableTiming));
-  if (he == hipSuccess) ok(hipEventCreateWithFlags(&c->acked, hipEventDisableTiming));
-  for (int p = 0; p < world && he == hipSuccess; ++p) {
-    ok(hipStreamCreateWithFlags(&c->cs[p], hipStreamNonBlocking));
-    if (he == hipSuccess) ok(hipEventCreateWithFlags(&c->cs_done[p], hipEventDisableTiming));
+  HIP_TRY(hipHostMalloc(c->seq_ring.out(), sizeof(uint64_t) * kCopySeqRing, hipHostMallocDefault));
+  HIP_TRY(hipHostMalloc(c->timeout_flag.out(), sizeof(uint32_t), hipHostMallocDefault));
+  *c->timeout_flag.get() = 0;
+  HIP_TRY(hipStreamCreateWithFlags(cm.stream.out(), hipStreamNonBlocking));
+  HIP_TRY(hipEventCreateWithFlags(cm.ready.out(), hipEventDisableTiming));
+  for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreateWithFlags(cm.done[k].out(), hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(c->acked.out(), hipEventDisableTiming));
+  for (int p = 0; p < world; ++p) {
+    HIP_TRY(hipStreamCreateWithFlags(c->cs[p].out(), hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(c->cs_done[p].out(), hipEventDisableTiming));
   }
   {
     // (default: the 8-byte copies and ONE waiting wavefront per wait -- a wait on W - 1 words is W - 1 stream operations, and at 8 ranks the
@@ -2610,26 +2616,18 @@ int rcsh_comm_copy_create(rcsh_sim* s, int32_t rank, int32_t world, size_t bytes
   }
   CopyBlob b{};
   b.magic = 0x52435348u; b.rank = (uint32_t)rank; b.bytes_per_rank = bytes_per_rank; b.device = s->device; b.pid = (int32_t)getpid();
-  for (int k = 0; k < 2 && he == hipSuccess; ++k) ok(hipIpcGetMemHandle(&b.recv[k], c->recv[k]));
-  if (he == hipSuccess) ok(hipIpcGetMemHandle(&b.flags, c->flags));
-  if (he != hipSuccess) {
-    if (s->comm_stream) hipStreamDestroy(s->comm_stream);
-    if (s->comm_ready) hipEventDestroy(s->comm_ready);
-    for (int k = 0; k < 2; ++k) if (s->comm_done[k]) hipEventDestroy(s->comm_done[k]);
-    s->comm_stream = nullptr; s->comm_ready = s->comm_done[0] = s->comm_done[1] = nullptr;
-    copy_carrier_free(s);
-    return fail(RCSH_ERR_DEVICE, std::string("copy carrier: ") + hipGetErrorString(he));
-  }
+  for (int k = 0; k < 2; ++k) HIP_TRY(hipIpcGetMemHandle(&b.recv[k], c->recv[k].get()));
+  HIP_TRY(hipIpcGetMemHandle(&b.flags, c->flags.get()));
   std::memset(blob, 0, RCSH_COMM_COPY_BLOB_BYTES);
   std::memcpy(blob, &b, sizeof(b));
-  s->comm_pending[0] = s->comm_pending[1] = false;
-  s->comm_rank = rank; s->comm_world = world;
+  cm.rank = rank; cm.world = world;
+  s->comm = std::move(cm);
   return RCSH_OK;
 }
 
 int rcsh_comm_copy_connect(rcsh_sim* s, const uint8_t* blobs) {
   REQUIRE_SIM(s);
-  CopyCarrier* c = s->copy;
+  CopyCarrier* c = s->comm.copy.get();
   if (!c) return fail(RCSH_ERR_STATE, "no copy carrier: call rcsh_comm_copy_create first");
   if (c->connected) return fail(RCSH_ERR_STATE, "the copy carrier is connected already");
   if (!blobs) return fail(RCSH_ERR_ARG, "null blobs");
@@ -2639,7 +2637,7 @@ int rcsh_comm_copy_connect(rcsh_sim* s, const uint8_t* blobs) {
     if (b.magic != 0x52435348u || (int)b.rank != p || b.bytes_per_rank != c->bytes)
       return fail(RCSH_ERR_ARG, "copy carrier: blob " + std::to_string(p) + " is not rank " + std::to_string(p) + "'s, or the ranks disagree on the block size");
     if (p == c->rank) {
-      c->peer_recv[p][0] = c->recv[0]; c->peer_recv[p][1] = c->recv[1]; c->peer_flags[p] = c->flags;
+      c->peer_recv[p][0] = c->recv[0].get(); c->peer_recv[p][1] = c->recv[1].get(); c->peer_flags[p] = c->flags.get();
       continue;
     }
     if (b.pid == (int32_t)getpid()) return fail(RCSH_ERR_ARG, "copy carrier: two ranks in one process (IPC handles open in another process only)");
@@ -2655,56 +2653,56 @@ int rcsh_comm_copy_connect(rcsh_sim* s, const uint8_t* blobs) {
 
 int rcsh_comm_copy_recv_buffer(rcsh_sim* s, int32_t slot, void** recv_dev) {
   REQUIRE_SIM(s);
-  if (!s->copy) return fail(RCSH_ERR_STATE, "no copy carrier: call rcsh_comm_copy_create first");
+  if (!s->comm.copy) return fail(RCSH_ERR_STATE, "no copy carrier: call rcsh_comm_copy_create first");
   if (slot < 0 || slot > 1 || !recv_dev) return fail(RCSH_ERR_ARG, "exchange slot is 0 or 1");
-  *recv_dev = s->copy->recv[slot];
+  *recv_dev = s->comm.copy.get()->recv[slot].get();
   return RCSH_OK;
 }
 
 namespace {
 int copy_allgather(rcsh_sim* s, int32_t slot, const void* send_dev, void* recv_dev, size_t bytes_per_rank) {
-  CopyCarrier* c = s->copy;
+  CopyCarrier* c = s->comm.copy.get();
   if (!c->connected) return fail(RCSH_ERR_STATE, "copy carrier: call rcsh_comm_copy_connect first");
-  if (recv_dev != c->recv[slot] || bytes_per_rank != c->bytes)
+  if (recv_dev != c->recv[slot].get() || bytes_per_rank != c->bytes)
     return fail(RCSH_ERR_ARG, "copy carrier: the receive buffer of a slot is the carrier's (rcsh_comm_copy_recv_buffer), the block size the one it was created with");
-  if (*c->timeout_flag) return fail(RCSH_ERR_DEVICE, "copy carrier: an earlier gather gave up waiting for a peer");
+  if (*c->timeout_flag.get()) return fail(RCSH_ERR_DEVICE, "copy carrier: an earlier gather gave up waiting for a peer");
   const int me = c->rank, W = c->world;
   auto flag = [&](uint64_t* base, int kind, int sl, int r) { return base + ((size_t)kind * 2 + sl) * kCopyMaxWorld + r; };
   // after what the handle's stream holds so far: the env-step that wrote the send buffer, the consumer of this slot's last gather
-  HIP_TRY(hipEventRecord(s->comm_ready, s->stream));
-  HIP_TRY(hipStreamWaitEvent(s->comm_stream, s->comm_ready, 0));
+  HIP_TRY(hipEventRecord(s->comm.ready.get(), s->stream));
+  HIP_TRY(hipStreamWaitEvent(s->comm.stream.get(), s->comm.ready.get(), 0));
   if (c->use_graph && !c->stream_values) {
     if (c->gexec[slot] && c->gsend[slot] != send_dev) {  // (another send buffer: the copies' source is part of the graph)
       hipGraphExecDestroy(c->gexec[slot]); hipGraphDestroy(c->graph[slot]);
       c->gexec[slot] = nullptr; c->graph[slot] = nullptr;
     }
     if (!c->gexec[slot]) {
-      uint64_t* qd = c->qdev + slot;
-      hipError_t ge = hipStreamBeginCapture(s->comm_stream, hipStreamCaptureModeThreadLocal);
+      uint64_t* qd = c->qdev.get() + slot;
+      hipError_t ge = hipStreamBeginCapture(s->comm.stream.get(), hipStreamCaptureModeThreadLocal);
       auto g = [&](hipError_t e_) { if (ge == hipSuccess) ge = e_; };
       if (ge == hipSuccess) {
-        hipLaunchKernelGGL(k_bump, dim3(1), dim3(1), 0, s->comm_stream, qd);
+        hipLaunchKernelGGL(k_bump, dim3(1), dim3(1), 0, s->comm.stream.get(), qd);
         g(hipGetLastError());
         for (int p = 0; p < W; ++p)
-          if (p != me) g(hipMemcpyAsync(flag(c->peer_flags[p], 0, slot, me), qd, sizeof(uint64_t), hipMemcpyDeviceToDevice, s->comm_stream));
+          if (p != me) g(hipMemcpyAsync(flag(c->peer_flags[p], 0, slot, me), qd, sizeof(uint64_t), hipMemcpyDeviceToDevice, s->comm.stream.get()));
         if (W > 1) {
-          hipLaunchKernelGGL(k_wait_flags_at, dim3(1), dim3(64), 0, s->comm_stream, flag(c->flags, 0, slot, 0), W, me, qd, c->timeout_flag);
+          hipLaunchKernelGGL(k_wait_flags_at, dim3(1), dim3(64), 0, s->comm.stream.get(), flag(c->flags.get(), 0, slot, 0), W, me, qd, c->timeout_flag.get());
           g(hipGetLastError());
         }
-        g(hipEventRecord(c->acked, s->comm_stream));
+        g(hipEventRecord(c->acked.get(), s->comm.stream.get()));
         for (int p = 0; p < W; ++p) {
-          g(hipStreamWaitEvent(c->cs[p], c->acked, 0));
-          g(hipMemcpyAsync((char*)c->peer_recv[p][slot] + (size_t)me * c->bytes, send_dev, c->bytes, hipMemcpyDeviceToDevice, c->cs[p]));
-          if (p != me) g(hipMemcpyAsync(flag(c->peer_flags[p], 1, slot, me), qd, sizeof(uint64_t), hipMemcpyDeviceToDevice, c->cs[p]));
-          g(hipEventRecord(c->cs_done[p], c->cs[p]));
-          g(hipStreamWaitEvent(s->comm_stream, c->cs_done[p], 0));
+          g(hipStreamWaitEvent(c->cs[p].get(), c->acked.get(), 0));
+          g(hipMemcpyAsync((char*)c->peer_recv[p][slot] + (size_t)me * c->bytes, send_dev, c->bytes, hipMemcpyDeviceToDevice, c->cs[p].get()));
+          if (p != me) g(hipMemcpyAsync(flag(c->peer_flags[p], 1, slot, me), qd, sizeof(uint64_t), hipMemcpyDeviceToDevice, c->cs[p].get()));
+          g(hipEventRecord(c->cs_done[p].get(), c->cs[p].get()));
+          g(hipStreamWaitEvent(s->comm.stream.get(), c->cs_done[p].get(), 0));
         }
         if (W > 1) {
-          hipLaunchKernelGGL(k_wait_flags_at, dim3(1), dim3(64), 0, s->comm_stream, flag(c->flags, 1, slot, 0), W, me, qd, c->timeout_flag);
+          hipLaunchKernelGGL(k_wait_flags_at, dim3(1), dim3(64), 0, s->comm.stream.get(), flag(c->flags.get(), 1, slot, 0), W, me, qd, c->timeout_flag.get());
           g(hipGetLastError());
         }
         hipGraph_t gr = nullptr;
-        const hipError_t ee = hipStreamEndCapture(s->comm_stream, &gr);
+        const hipError_t ee = hipStreamEndCapture(s->comm.stream.get(), &gr);
         if (ge == hipSuccess) ge = ee;
         if (ge == hipSuccess) ge = hipGraphInstantiate(&c->gexec[slot], gr, nullptr, nullptr, 0);
         if (ge == hipSuccess) { c->graph[slot] = gr; c->gsend[slot] = send_dev; }
@@ -2719,14 +2717,14 @@ int copy_allgather(rcsh_sim* s, int32_t slot, const void* send_dev, void* recv_d
     }
     if (c->gexec[slot]) {
       ++c->seq[slot];
-      HIP_TRY(hipGraphLaunch(c->gexec[slot], s->comm_stream));
-      HIP_TRY(hipEventRecord(s->comm_done[slot], s->comm_stream));
-      s->comm_pending[slot] = true;
+      HIP_TRY(hipGraphLaunch(c->gexec[slot], s->comm.stream.get()));
+      HIP_TRY(hipEventRecord(s->comm.done[slot].get(), s->comm.stream.get()));
+      s->comm.pending[slot] = true;
       return RCSH_OK;
     }
   }
   const uint64_t q = ++c->seq[slot];
-  uint64_t* qsrc = c->seq_ring + (c->ring_pos++ % kCopySeqRing);
+  uint64_t* qsrc = c->seq_ring.get() + (c->ring_pos++ % kCopySeqRing);
   *qsrc = q;
   auto write_word = [&](hipStream_t st, uint64_t* dst) -> hipError_t {
     if (c->stream_values) return hipStreamWriteValue64(st, dst, q, 0);
@@ -2742,26 +2740,26 @@ int copy_allgather(rcsh_sim* s, int32_t slot, const void* send_dev, void* recv_d
       }
       return hipSuccess;
     }
-    hipLaunchKernelGGL(k_wait_flags, dim3(1), dim3(64), 0, st, base, W, me, q, c->timeout_flag);
+    hipLaunchKernelGGL(k_wait_flags, dim3(1), dim3(64), 0, st, base, W, me, q, c->timeout_flag.get());
     return hipGetLastError();
   };
   // 1. tell every peer that this rank's receive buffer of the slot is free for q; wait until every peer has said so
   for (int p = 0; p < W; ++p)
-    if (p != me) HIP_TRY(write_word(s->comm_stream, flag(c->peer_flags[p], 0, slot, me)));
-  HIP_TRY(wait_words(s->comm_stream, flag(c->flags, 0, slot, 0)));
-  HIP_TRY(hipEventRecord(c->acked, s->comm_stream));
+    if (p != me) HIP_TRY(write_word(s->comm.stream.get(), flag(c->peer_flags[p], 0, slot, me)));
+  HIP_TRY(wait_words(s->comm.stream.get(), flag(c->flags.get(), 0, slot, 0)));
+  HIP_TRY(hipEventRecord(c->acked.get(), s->comm.stream.get()));
   // 2. the block to every peer, each over its own stream (its own link), followed by the word that says it has arrived
   for (int p = 0; p < W; ++p) {
-    HIP_TRY(hipStreamWaitEvent(c->cs[p], c->acked, 0));
-    HIP_TRY(hipMemcpyAsync((char*)c->peer_recv[p][slot] + (size_t)me * c->bytes, send_dev, c->bytes, hipMemcpyDeviceToDevice, c->cs[p]));
-    if (p != me) HIP_TRY(write_word(c->cs[p], flag(c->peer_flags[p], 1, slot, me)));
-    HIP_TRY(hipEventRecord(c->cs_done[p], c->cs[p]));
-    HIP_TRY(hipStreamWaitEvent(s->comm_stream, c->cs_done[p], 0));  // (the send buffer is free once these have run)
+    HIP_TRY(hipStreamWaitEvent(c->cs[p].get(), c->acked.get(), 0));
+    HIP_TRY(hipMemcpyAsync((char*)c->peer_recv[p][slot] + (size_t)me * c->bytes, send_dev, c->bytes, hipMemcpyDeviceToDevice, c->cs[p].get()));
+    if (p != me) HIP_TRY(write_word(c->cs[p].get(), flag(c->peer_flags[p], 1, slot, me)));
+    HIP_TRY(hipEventRecord(c->cs_done[p].get(), c->cs[p].get()));
+    HIP_TRY(hipStreamWaitEvent(s->comm.stream.get(), c->cs_done[p].get(), 0));  // (the send buffer is free once these have run)
   }
   // 3. the slot is gathered when every peer's block has arrived here
-  HIP_TRY(wait_words(s->comm_stream, flag(c->flags, 1, slot, 0)));
-  HIP_TRY(hipEventRecord(s->comm_done[slot], s->comm_stream));
-  s->comm_pending[slot] = true;
+  HIP_TRY(wait_words(s->comm.stream.get(), flag(c->flags.get(), 1, slot, 0)));
+  HIP_TRY(hipEventRecord(s->comm.done[slot].get(), s->comm.stream.get()));
+  s->comm.pending[slot] = true;
   return RCSH_OK;
 }
 }  // namespace
@@ -2795,6 +2793,7 @@ static Rccl& rccl() {
   if (!r.GetUniqueId || !r.CommInitRank || !r.AllGather || !r.CommDestroy || !r.GetErrorString) r.why = "librccl.so lacks the collective entry points";
   return r;
 }
+void rccl_comm_destroy(void* comm) { rccl().CommDestroy(comm); }
 #define RCCL_TRY(expr)                                                                                             \
   do {                                                                                                             \
     const int _e = (expr);                                                                                         \
@@ -2815,7 +2814,7 @@ int rcsh_comm_get_unique_id(uint8_t id[RCSH_COMM_ID_BYTES]) {
 int rcsh_comm_init(rcsh_sim* s, const uint8_t id[RCSH_COMM_ID_BYTES], int32_t rank, int32_t world) {
   REQUIRE_SIM(s);
   if (!id || world < 1 || rank < 0 || rank >= world) return fail(RCSH_ERR_ARG, "communicator: need an id and 0 <= rank < world");
-  if (s->comm) return fail(RCSH_ERR_STATE, "a communicator is already attached to this sim");
+  if (s->comm.nccl) return fail(RCSH_ERR_STATE, "a communicator is already attached to this sim");
   Rccl& r = rccl();
   if (!r.why.empty()) return fail(RCSH_ERR_DEVICE, r.why);
   Rccl::UniqueId u;
@@ -2824,44 +2823,40 @@ int rcsh_comm_init(rcsh_sim* s, const uint8_t id[RCSH_COMM_ID_BYTES], int32_t ra
   // called hipSetDevice itself (a plain C host has no reason to) must not end up with every rank on device 0
   HIP_TRY(hipSetDevice(s->device));
   // stream and events first: they cannot fail collectively, ncclCommInitRank can only be entered by all ranks or none
-  hipError_t he = hipStreamCreateWithFlags(&s->comm_stream, hipStreamNonBlocking);
-  if (he == hipSuccess) he = hipEventCreateWithFlags(&s->comm_ready, hipEventDisableTiming);
-  for (int k = 0; k < 2 && he == hipSuccess; ++k) he = hipEventCreateWithFlags(&s->comm_done[k], hipEventDisableTiming);
-  int nrc = 0;
-  if (he == hipSuccess) nrc = r.CommInitRank(&s->comm, world, u, rank);
-  if (he != hipSuccess || nrc != 0) {
-    if (s->comm_stream) hipStreamDestroy(s->comm_stream);
-    if (s->comm_ready) hipEventDestroy(s->comm_ready);
-    for (int k = 0; k < 2; ++k) if (s->comm_done[k]) hipEventDestroy(s->comm_done[k]);
-    s->comm = nullptr; s->comm_stream = nullptr; s->comm_ready = s->comm_done[0] = s->comm_done[1] = nullptr;
-    if (he != hipSuccess) return fail(RCSH_ERR_DEVICE, std::string("communicator stream / events: ") + hipGetErrorString(he));
+  rcsh_sim::Comm cm;  // (attached at the end: a failure leaves the handle without any of it)
+  hipError_t he = hipStreamCreateWithFlags(cm.stream.out(), hipStreamNonBlocking);
+  if (he == hipSuccess) he = hipEventCreateWithFlags(cm.ready.out(), hipEventDisableTiming);
+  for (int k = 0; k < 2 && he == hipSuccess; ++k) he = hipEventCreateWithFlags(cm.done[k].out(), hipEventDisableTiming);
+  if (he != hipSuccess) return fail(RCSH_ERR_DEVICE, std::string("communicator stream / events: ") + hipGetErrorString(he));
+  void* comm = nullptr;
+  if (const int nrc = r.CommInitRank(&comm, world, u, rank))
     return fail(RCSH_ERR_DEVICE, std::string("ncclCommInitRank: ") + (r.GetErrorString ? r.GetErrorString(nrc) : "error ") + " (" + std::to_string(nrc) + ")");
-  }
-  s->comm_pending[0] = s->comm_pending[1] = false;
-  s->comm_rank = rank;
-  s->comm_world = world;
+  cm.nccl.reset(comm);
+  cm.rank = rank;
+  cm.world = world;
+  s->comm = std::move(cm);
   return RCSH_OK;
 }
 
 int rcsh_comm_rank(const rcsh_sim* s, int32_t* rank, int32_t* world) {
   if (!s) return fail(RCSH_ERR_ARG, "null sim handle");
-  if (rank) *rank = s->comm_rank;
-  if (world) *world = s->comm_world;
+  if (rank) *rank = s->comm.rank;
+  if (world) *world = s->comm.world;
   return RCSH_OK;
 }
 
 int rcsh_comm_allgather_dev(rcsh_sim* s, int32_t slot, const void* send_dev, void* recv_dev, size_t bytes_per_rank) {
   REQUIRE_SIM(s);
-  if (!s->comm && !s->copy) return fail(RCSH_ERR_STATE, "no communicator: call rcsh_comm_init (or rcsh_comm_copy_create) first");
+  if (!s->comm.nccl && !s->comm.copy) return fail(RCSH_ERR_STATE, "no communicator: call rcsh_comm_init (or rcsh_comm_copy_create) first");
   if (!send_dev || !recv_dev) return fail(RCSH_ERR_ARG, "null buffer");
   if (slot < 0 || slot > 1) return fail(RCSH_ERR_ARG, "exchange slot is 0 or 1");
-  if (s->copy) return copy_allgather(s, slot, send_dev, recv_dev, bytes_per_rank);
+  if (s->comm.copy) return copy_allgather(s, slot, send_dev, recv_dev, bytes_per_rank);
   // after what the handle's stream holds so far (the env-step that wrote the observations), on the communicator's stream
-  HIP_TRY(hipEventRecord(s->comm_ready, s->stream));
-  HIP_TRY(hipStreamWaitEvent(s->comm_stream, s->comm_ready, 0));
-  RCCL_TRY(rccl().AllGather(send_dev, recv_dev, bytes_per_rank, /* ncclInt8 */ 0, s->comm, s->comm_stream));
-  HIP_TRY(hipEventRecord(s->comm_done[slot], s->comm_stream));
-  s->comm_pending[slot] = true;
+  HIP_TRY(hipEventRecord(s->comm.ready.get(), s->stream));
+  HIP_TRY(hipStreamWaitEvent(s->comm.stream.get(), s->comm.ready.get(), 0));
+  RCCL_TRY(rccl().AllGather(send_dev, recv_dev, bytes_per_rank, /* ncclInt8 */ 0, s->comm.nccl.get(), s->comm.stream.get()));
+  HIP_TRY(hipEventRecord(s->comm.done[slot].get(), s->comm.stream.get()));
+  s->comm.pending[slot] = true;
   return RCSH_OK;
 }
 
@@ -2872,33 +2867,30 @@ int rcsh_env_allgather_obs_dev(rcsh_sim* s, int32_t slot, const double* local_ob
 
 int rcsh_comm_wait(rcsh_sim* s, int32_t slot, int32_t block_host) {
   REQUIRE_SIM(s);
-  if (!s->comm && !s->copy) return fail(RCSH_ERR_STATE, "no communicator: call rcsh_comm_init (or rcsh_comm_copy_create) first");
+  if (!s->comm.nccl && !s->comm.copy) return fail(RCSH_ERR_STATE, "no communicator: call rcsh_comm_init (or rcsh_comm_copy_create) first");
   if (slot < 0 || slot > 1) return fail(RCSH_ERR_ARG, "exchange slot is 0 or 1");
-  if (!s->comm_pending[slot]) return RCSH_OK;
+  if (!s->comm.pending[slot]) return RCSH_OK;
   if (block_host) {
-    HIP_TRY(hipEventSynchronize(s->comm_done[slot]));
-    if (s->copy && *s->copy->timeout_flag) return fail(RCSH_ERR_DEVICE, "copy carrier: gave up waiting for a peer's block (a rank died?)");
-    s->comm_pending[slot] = false;  // (a stream-side wait leaves it set: a later host-side wait must still see the event)
+    HIP_TRY(hipEventSynchronize(s->comm.done[slot].get()));
+    if (s->comm.copy && *s->comm.copy.get()->timeout_flag.get()) return fail(RCSH_ERR_DEVICE, "copy carrier: gave up waiting for a peer's block (a rank died?)");
+    s->comm.pending[slot] = false;  // (a stream-side wait leaves it set: a later host-side wait must still see the event)
   } else {
     // (a stream-side wait cannot see a gather give up while it is in flight; it refuses to order consumers behind a carrier that HAS
     // given up on a peer -- the pinned flag, host-readable at any time: every later wait and post fails until the carrier is rebuilt;
     // advisor, round 5)
-    if (s->copy && *s->copy->timeout_flag) return fail(RCSH_ERR_DEVICE, "copy carrier: an earlier gather gave up waiting for a peer's block (a rank died?)");
-    HIP_TRY(hipStreamWaitEvent(s->stream, s->comm_done[slot], 0));
+    if (s->comm.copy && *s->comm.copy.get()->timeout_flag.get()) return fail(RCSH_ERR_DEVICE, "copy carrier: an earlier gather gave up waiting for a peer's block (a rank died?)");
+    HIP_TRY(hipStreamWaitEvent(s->stream, s->comm.done[slot].get(), 0));
   }
   return RCSH_OK;
 }
 
 int rcsh_comm_destroy(rcsh_sim* s) {
   REQUIRE_SIM(s);
-  if (!s->comm && !s->copy) return RCSH_OK;
-  hipStreamSynchronize(s->comm_stream);
-  if (s->copy) copy_carrier_free(s);
-  else rccl().CommDestroy(s->comm);
-  hipEventDestroy(s->comm_ready); hipEventDestroy(s->comm_done[0]); hipEventDestroy(s->comm_done[1]);
-  hipStreamDestroy(s->comm_stream);
-  s->comm = nullptr; s->comm_stream = nullptr; s->comm_ready = s->comm_done[0] = s->comm_done[1] = nullptr; s->comm_pending[0] = s->comm_pending[1] = false;
-  s->comm_rank = 0; s->comm_world = 1;
+  if (!s->comm.nccl && !s->comm.copy) return RCSH_OK;
+  hipStreamSynchronize(s->comm.stream.get());
+  // the one teardown: `gone` is destroyed on return, its members in reverse -- the carrier or the communicator, the events, the stream
+  rcsh_sim::Comm gone = std::move(s->comm);
+  s->comm = rcsh_sim::Comm{};
   return RCSH_OK;
 }
 
@@ -3010,12 +3002,13 @@ int rcsh_debug_dump_model(rcsh_sim* s, void* buf, size_t cap, size_t* size) {
 int rcsh_prof_enable(rcsh_sim* s, int32_t enable) {
   REQUIRE_SIM(s);
   if (enable && s->ev_start.empty()) {
-    s->ev_start.resize(kProfRing);
-    s->ev_stop.resize(kProfRing);
+    std::vector<Event> start(kProfRing), stop(kProfRing);  // (attached when all of them exist)
     for (int i = 0; i < kProfRing; ++i) {
-      HIP_TRY(hipEventCreate(&s->ev_start[i]));
-      HIP_TRY(hipEventCreate(&s->ev_stop[i]));
+      HIP_TRY(hipEventCreate(start[i].out()));
+      HIP_TRY(hipEventCreate(stop[i].out()));
     }
+    s->ev_start = std::move(start);
+    s->ev_stop = std::move(stop);
   }
   s->prof = enable != 0;
   s->prof_region = enable < 0;
@@ -3030,9 +3023,9 @@ int rcsh_prof_read(rcsh_sim* s, double* total_ms, int64_t* launches) {
   if (s->prof_region) {
     float ms = 0.f;
     if (s->prof_region_launches > 0) {
-      HIP_TRY(hipEventRecord(s->ev_stop[0], s->stream));
-      HIP_TRY(hipEventSynchronize(s->ev_stop[0]));
-      HIP_TRY(hipEventElapsedTime(&ms, s->ev_start[0], s->ev_stop[0]));
+      HIP_TRY(hipEventRecord(s->ev_stop[0].get(), s->stream));
+      HIP_TRY(hipEventSynchronize(s->ev_stop[0].get()));
+      HIP_TRY(hipEventElapsedTime(&ms, s->ev_start[0].get(), s->ev_stop[0].get()));
     }
     if (total_ms) *total_ms = ms;
     if (launches) *launches = s->prof_region_launches;

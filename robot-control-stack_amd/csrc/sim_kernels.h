@@ -288,26 +288,6 @@ struct EnvRegs {
   int32_t conv_steps;
 };
 
-template <class T, class ST>
-__device__ __forceinline__ void load_env(const Params& P, int e, EnvRegs<T, ST>& r) {
-  using L = Lay<T>;
-  const int n = P.n;
-  const double* S = P.S;
-#pragma unroll
-  for (int i = 0; i < T::NL; ++i) { r.st.q(i) = S[(L::QPOS + i) * n + e]; r.st.v(i) = S[(L::QVEL + i) * n + e]; r.st.qpre(i) = P.keep_qpre ? S[(L::QPRE + i) * n + e] : 0.0; }
-#pragma unroll
-  for (int i = 0; i < T::NU; ++i) r.st.c(i) = S[(L::CTRL + i) * n + e];
-  r.time = S[L::TIME * n + e];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) r.cb(i) = S[(L::CB + i) * n + e];
-#pragma unroll
-  for (int i = 0; i < T::NARM; ++i) { r.prevq(i) = S[(L::PREVQ + i) * n + e]; r.target(i) = S[(L::TARGET + i) * n + e]; }
-  r.last_cmd_width = S[(L::GRIP + 0) * n + e];
-  r.last_width = S[(L::GRIP + 1) * n + e];
-  r.flags = P.flags[e];
-  r.conv_steps = P.conv_steps[e];
-}
-
 // kStaged false: only the fields EnvRegs holds in registers (the team kernel moves the LDS-staged ones with all
 // 16 lanes of the team, team_staged_fields)
 template <class T, class ST, bool kStaged = true>
@@ -522,91 +502,8 @@ struct StepInStaged {
   __device__ __forceinline__ float gripper() const { return (float)s[4 * T::NARM]; }
 };
 
-// Wrappers' reset() / action() side effects on one environment: everything env.reset() / env.step() do before
-// the simulator is stepped (reference python/rcs/envs/base.py, envs/sim.py; see the inline citations).
-template <class T, class ST, class In>
-__device__ __forceinline__ void env_prologue(const Params& P, const RunOp& op, const DevModelHead& m, int e, EnvRegs<T, ST>& r, const In& in) {
-  using L = Lay<T>;
-  const int n = P.n;
-  if (op.do_reset) {
-    // GripperWrapper.reset -> SimGripper::m_reset (python/rcs/envs/base.py:703-708, SimGripper.cpp:158-165)
-    if (T::GRIP && P.grip.present) {
-      r.last_cmd_width = 0; r.last_width = 0;
-      r.flags &= ~(kGripMoving | kGripCollision | kHasGripCmd | kGripCmd);
-    }
-    // RobotSimWrapper.reset -> Sim::reset = mj_resetData + reset_callbacks (envs/sim.py:68-76, sim.cpp:117-138);
-    // it overwrites what the gripper reset just wrote to qpos / ctrl
-#pragma unroll
-    for (int i = 0; i < T::NL; ++i) { r.st.q(i) = m.qpos0[i]; r.st.v(i) = 0; }
-#pragma unroll
-    for (int i = 0; i < T::NU; ++i) r.st.c(i) = 0;
-    r.time = 0;
-    r.flags &= ~(kContactOverflow | kContactUnresolved | kContactResolved | kEscQuiet);  // (sticky until Sim::reset: this is it)
-#pragma unroll
-    for (int i = 0; i < 6; ++i) r.cb(i) = 0;
-    // RobotEnv.reset -> SimRobot::m_reset -> set_joints_hard(q_home) (base.py:290-304, SimRobot.cpp:193-205)
-#pragma unroll
-    for (int i = 0; i < T::NARM; ++i) { r.st.q(i) = P.robot.q_home[i]; r.st.c(i) = P.robot.q_home[i]; }
-  }
-
-  if (op.apply_action) {
-    // ---- RelativeActionSpace.action (python/rcs/envs/base.py:468-488), JOINTS mode
-    double a[T::NARM];
-#pragma unroll
-    for (int i = 0; i < T::NARM; ++i) a[i] = in.action(i);
-    if (P.env.relative_to != 0) {
-      const bool last_step = P.env.relative_to == 1;
-      const bool fresh = last_step || !(r.flags & kHasLastAction);
-#pragma unroll
-      for (int i = 0; i < T::NARM; ++i) {
-        double origin = last_step ? r.st.q(i) : in.origin(i);
-        double lim;
-        if (fresh) {
-          lim = clampd(a[i], -P.env.max_mov[0], P.env.max_mov[0]);
-        } else {
-          const double la = in.lasta(i);
-          lim = clampd(a[i] - la, -P.env.max_mov[0], P.env.max_mov[0]) + la;
-        }
-        if (last_step) P.S[(L::ORIGIN + i) * n + e] = origin;
-        P.S[(L::LASTA + i) * n + e] = lim;
-        a[i] = clampd(origin + lim, P.env.low[i], P.env.high[i]);
-      }
-      r.flags |= kHasLastAction;
-    }
-    // ---- CollisionGuard (guard_team.h): a blocked environment is commanded to stay where it is
-    if (op.apply_action == 2 && (op.mask[e] & 2)) {
-#pragma unroll
-      for (int i = 0; i < T::NARM; ++i) a[i] = r.st.q(i);
-    }
-    // ---- GripperWrapper.action (base.py:721-735)
-    if (T::GRIP && P.grip.present && op.gripper) {
-      float g = in.gripper();
-      if (P.env.binary_gripper) g = rintf(g);  // np.round: half to even
-      g = fminf(fmaxf(g, 0.0f), 1.0f);
-      if (P.env.binary_gripper) {
-        gripper_set_width<T, ST>(P, r, g == 0.0f ? 0.0 : 1.0);  // grasp() = shut() : open()
-        set_flag(r.flags, kGripCmd, g != 0.0f);
-      } else {
-        gripper_set_width<T, ST>(P, r, (double)g);
-        set_flag(r.flags, kGripCmd, g >= 0.5f);
-      }
-      r.flags |= kHasGripCmd;
-    }
-    // ---- RobotEnv.step (base.py:255-288): command only when the action moved by more than atol = 1e-3
-    bool changed = !(r.flags & kHasPrevAction);
-#pragma unroll
-    for (int i = 0; i < T::NARM; ++i) {
-      const double pa = in.preva(i);
-      changed = changed || !(fabs(a[i] - pa) <= 1e-3);
-      P.S[(L::PREVA + i) * n + e] = a[i];
-    }
-    if (changed) robot_set_joint_position<T, ST>(r, a);
-    r.flags |= kHasPrevAction;
-  }
-
-}
-
-// The same on the team's lanes: lane i does joint i of everything that is per joint (the relative action's clamps and
+// Wrappers' reset() / action() side effects on one environment: everything env.reset() / env.step() do before the simulator is
+// stepped (reference python/rcs/envs/base.py, envs/sim.py; see the inline citations), on the team's lanes: lane i does joint i of everything that is per joint (the relative action's clamps and
 // remembered vectors, the "did the action move" test, SimRobot::set_joint_position), the leader lane what is per environment
 // (gripper, flags, clocks).  Per-joint inputs arrive in the lane's registers (in_*), the leader's flag word is spread to the team
 // first.  One lane walking the seven joints through LDS took 5.1k cycles of every launch.  Every lane of a live team calls this.

@@ -46,14 +46,8 @@ RCSH_D double row_up_or(double old, double x) {
   const int hi = __builtin_amdgcn_update_dpp(hi32(old), hi32(x), 0x110 + N, 0xf, 0xf, false);
   return mk64(hi, lo);
 }
-// the same, delivered only to the lanes of the 4-lane banks selected by BANKS (bit b: lanes 4b..4b+3 of every
-// row); all other lanes receive zero / `old`
-template <int N, int BANKS>
-RCSH_D double row_up_banks(double x) {
-  const int lo = __builtin_amdgcn_update_dpp(0, lo32(x), 0x110 + N, 0xf, BANKS, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, hi32(x), 0x110 + N, 0xf, BANKS, false);
-  return mk64(hi, lo);
-}
+// row_up_or delivered only to the lanes of the 4-lane banks selected by BANKS (bit b: lanes 4b..4b+3 of every
+// row); all other lanes keep `old`
 template <int N, int BANKS>
 RCSH_D double row_up_or_banks(double old, double x) {
   const int lo = __builtin_amdgcn_update_dpp(lo32(old), lo32(x), 0x110 + N, 0xf, BANKS, false);
