@@ -797,7 +797,18 @@ RCSH_D bool unresolved_contact_check(const CheckTable& ck, const ContactTable& t
       Shape B = make_shape(b.type == 7 ? 0 : b.type == 6 ? 1 : 2, pb, Rb, b.size, stage + na, b.vert_num);
       if (a.type == 7) { mulmv(Ra, a.center, A.center); A.center[0] += pa[0]; A.center[1] += pa[1]; A.center[2] += pa[2]; }
       if (b.type == 7) { mulmv(Rb, b.center, B.center); B.center[0] += pb[0]; B.center[1] += pb[1]; B.center[2] += pb[2]; }
-      // the slot of this pair: the one that holds it, else the first empty one, else slot (pair index mod the number of slots)
+      // the slot of this pair: the one that holds it, else the first empty one, else slot (pair index mod the number of slots).
+      // WHICH pair finds a slot empty depends on the environment's neighbours: a round's pair is that of the wavefront's lowest lane
+      // with work, and every team that holds the same pair takes the round with it -- so the order in which a team meets its own pairs
+      // (and, under all_hit, how many of them it meets before the loop ends) follows from what the other three teams hold.  The slots
+      // are a cache of hints -- a remembered direction that no longer certifies falls through to the iteration below, and every
+      // way of failing is conservative --, so Lay::SEP is the one part of an environment's state that is NOT a function of its own
+      // inputs alone (tests/test_gpu_escalation_layouts.py holds everything else to bit equality across batch layouts).  What
+      // inherits the dependence: the direction that proves a pair apart -- the remembered one, or the one the iteration finds --
+      // sets gcert, the pair's new slack (slack_env, outside the state blob: no test compares it), which decides in which later
+      // launches the pair is due; and a remembered direction can pass certified() where the iteration's does not, or the other
+      // way round, which decides the environment's `now` bit.  That the bits and everything else come out equal across layouts is
+      // what the tests measure, not what this code guarantees: a layout that differs in escalated.now is to be looked for here.
       int s_hold = -1, s_free = -1;
 #pragma unroll
       for (int k = kCheckSlots - 1; k >= 0; --k) {
