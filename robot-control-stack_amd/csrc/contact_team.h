@@ -301,6 +301,7 @@ struct Shape {
   const double* verts;
   int nvert;
   double center[3];
+  int span = kTeamLanes;  // lanes that share a hull's vertex scan (wave-uniform; 32 or 64 only where the single-pass scan is asked for)
 };
 RCSH_D Shape make_shape(int type, const double* p, const double* R, const double* size, const double* verts, int nvert) {
   Shape s;
@@ -322,8 +323,23 @@ constexpr double kSupportTie = 1e-10;
 // LDS, scan every 16th vertex each, agree on the largest projection with four row rotations, then each lane looks for its
 // first vertex inside the band and the team takes the lowest index -- a lane scanning global memory alone pays a full round
 // trip per vertex, its wavefront having nothing else to run.
+// ONE = true takes a SPAN: the 16, 32 or 64 lanes (wave-uniform, aligned) that share the scan.  A 152-vertex hull is ten vertices a
+// lane and three trips for a team of 16, three vertices and one trip for the wavefront.  Wider than a DPP row, the rows' results are
+// combined through the four rows' first lanes (span_max, span_min_index): max and min are exact, the set of products is the same one
+// however it is dealt out, so the index is the 16-lane form's for every input, ties included.
+RCSH_D double span_max(double x, int span) {  // x: the row's value in each of its lanes
+  const double r0 = wave_read(x, 0), r1 = wave_read(x, 16), r2 = wave_read(x, 32), r3 = wave_read(x, 48);
+  const double lo = fmax(r0, r1), hi = fmax(r2, r3);
+  // (a span of 32: the other half of the wavefront may be refining another pair, or be switched off -- its rows are not looked at)
+  return span == 64 ? fmax(lo, hi) : ((threadIdx.x & 32) ? hi : lo);
+}
+RCSH_D int span_min_index(int x, int span) {
+  const int r0 = __builtin_amdgcn_readlane(x, 0), r1 = __builtin_amdgcn_readlane(x, 16), r2 = __builtin_amdgcn_readlane(x, 32), r3 = __builtin_amdgcn_readlane(x, 48);
+  const int lo = r0 < r1 ? r0 : r1, hi = r2 < r3 ? r2 : r3;
+  return span == 64 ? (lo < hi ? lo : hi) : ((threadIdx.x & 32) ? hi : lo);
+}
 template <bool TEAM, bool ONE = false>
-RCSH_D int hull_support_index(const double* verts_, int nvert, const double* l) {
+RCSH_D int hull_support_index(const double* verts_, int nvert, const double* l, int span = kTeamLanes) {
   double bestv = -INFINITY;
   int bi = 0;
   if (!TEAM) {
@@ -345,26 +361,30 @@ RCSH_D int hull_support_index(const double* verts_, int nvert, const double* l) 
     // and the second question -- the first vertex inside the tie band -- is asked of them, not of LDS again (through round 6's first
     // half the scan ran twice: two thirds of a support query's instructions, and the support queries are four fifths of a portal
     // refinement's 43k cycles).  The same products, rounded the same way: the same index.
+    // (a wider span needs fewer trips: the guard skips them, and the second question skips their slots -- the span is brought into a
+    // scalar register for that: left in a vector register the guards are exec masks and every index a vector shift)
     constexpr int kTrips = (kHullMaxVerts + 4 * kTeamLanes - 1) / (4 * kTeamLanes);
+    span = __builtin_amdgcn_readfirstlane(span);
+    const int ts = threadIdx.x & (span - 1);
     double pv[kTrips][4];
 #pragma unroll
     for (int r = 0; r < kTrips; ++r) {
-      const int i0 = t + 4 * kTeamLanes * r;
+      const int i0 = ts + 4 * span * r;
 #pragma unroll
       for (int u = 0; u < 4; ++u) pv[r][u] = -INFINITY;
-      if (4 * kTeamLanes * r < nvert) {
+      if (4 * span * r < nvert) {
         // four vertices per trip: their reads go out together
         double x[4][3];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          const int i = i0 + u * kTeamLanes < nvert ? i0 + u * kTeamLanes : 0;
+          const int i = i0 + u * span < nvert ? i0 + u * span : 0;
           x[u][0] = verts[3 * i]; x[u][1] = verts[3 * i + 1]; x[u][2] = verts[3 * i + 2];
         }
         sched_fence();
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const double v = x[u][0] * l[0] + x[u][1] * l[1] + x[u][2] * l[2];
-          pv[r][u] = i0 + u * kTeamLanes < nvert ? v : -INFINITY;
+          pv[r][u] = i0 + u * span < nvert ? v : -INFINITY;
           if (pv[r][u] > bestv) bestv = pv[r][u];
         }
       }
@@ -373,13 +393,16 @@ RCSH_D int hull_support_index(const double* verts_, int nvert, const double* l) 
     bestv = fmax(bestv, row_rotate<4>(bestv));
     bestv = fmax(bestv, row_rotate<2>(bestv));
     bestv = fmax(bestv, row_rotate<1>(bestv));
+    if (span > kTeamLanes) bestv = span_max(bestv, span);
     const double band = bestv - kSupportTie;
     bi = 0x7fffffff;  // (a lane without a vertex in the band: the largest index, never wins)
 #pragma unroll
     for (int r = kTrips - 1; r >= 0; --r)
+      if (4 * span * r < nvert) {  // (a trip that did not run left nothing inside the band)
 #pragma unroll
-      for (int u = 3; u >= 0; --u)
-        if (pv[r][u] >= band) bi = t + 4 * kTeamLanes * r + u * kTeamLanes;  // descending: the lane's lowest index is kept
+        for (int u = 3; u >= 0; --u)
+          if (pv[r][u] >= band) bi = ts + 4 * span * r + u * span;  // descending: the lane's lowest index is kept
+      }
   } else {
     for (int i0 = t; i0 < nvert; i0 += 4 * kTeamLanes) {
       // four vertices per trip: their reads go out together
@@ -425,6 +448,9 @@ RCSH_D int hull_support_index(const double* verts_, int nvert, const double* l) 
   }
   RCSH_ROT_MIN(8) RCSH_ROT_MIN(4) RCSH_ROT_MIN(2) RCSH_ROT_MIN(1)
 #undef RCSH_ROT_MIN
+  if constexpr (ONE) {
+    if (span > kTeamLanes) bi = span_min_index(bi, span);
+  }
   return bi;
 }
 template <bool TEAM = false, bool ONE = false>
@@ -432,7 +458,7 @@ RCSH_D void shape_support(const Shape& s, const double* dir, double* out) {
   double l[3], w[3] = {0, 0, 0};
   mulTv(s.R, dir, l);
   if (s.type == 0) {
-    const int bi = hull_support_index<TEAM, ONE>(s.verts, s.nvert, l);
+    const int bi = hull_support_index<TEAM, ONE>(s.verts, s.nvert, l, s.span);
     const double* vv = TEAM ? in_lds(s.verts) : s.verts;
     w[0] = vv[3 * bi]; w[1] = vv[3 * bi + 1]; w[2] = vv[3 * bi + 2];
   } else if (s.type == 1) {
@@ -1832,7 +1858,9 @@ RCSH_CONTACT_FN uint32_t contact_collide(const ContactTable& tab_, const CheckTa
     // the vertex scans of a hull's support queries), and the wavefront has four: up to FOUR pairs are refined side by side, a team each --
     // the lead pair (the first one pending) and pending pairs that need no hull but the lead's, in the lead's places (a hand pressed
     // against link 0 or 1 brings its ten pad boxes and two finger hulls near that link's hull at once: twelve refinements of 40k cycles
-    // one after the other were 500k of a substep's 800k).  Which pairs are refined together changes no pair's result.
+    // one after the other were 500k of a substep's 800k).  Two different hull-hull pairs never share a round, and that is a folded arm's usual
+    // round: a lone pair is given all 64 lanes, two pairs 32 each (the support query's span, hull_support_index).  Which pairs are refined
+    // together, and over how many lanes, changes no pair's result.
     for (uint64_t pend = __ballot(cm != 0); pend; pend = __ballot(cm != 0)) {
       const int src = __ffsll((long long)pend) - 1;  // wave-uniform
       const uint32_t sm = (uint32_t)__builtin_amdgcn_readlane((int)cm, src);
@@ -1928,7 +1956,14 @@ RCSH_CONTACT_FN uint32_t contact_collide(const ContactTable& tab_, const CheckTa
       }
       __syncthreads();
       TEAM_MARK(20)
-      const int team = lane >> 4;
+      // the round's shape: a lone pair has the whole wavefront scan its hulls (a 152-vertex hull: three vertices a lane, one trip of the
+      // support query where a team of 16 makes three), two pairs have half of it each, three or four a team of 16 each -- every lane of a
+      // pair's span computes the pair's refinement, the span's first lane is read.  (ck.pad bit 7, RCSH_CHECK_SKIP=128: teams of 16
+      // in every round, what tests/test_gpu_wide_support.py compares against.)
+      // (bit 8, RCSH_CHECK_SKIP=256: only the two-pair round stays on teams of 16 -- to time that shape on its own)
+      const int slog = (ck.pad & 128) || ngrp > 2 ? 4 : (ngrp == 2 ? ((ck.pad & 256) ? 4 : 5) : 6);  // (wave-uniform)
+      TEAM_ROUND_SHAPE(ngrp)
+      const int team = lane >> slog;
       const bool mine_pair = team < ngrp;
       const uint32_t mg = team == 0 ? grp_g[0] : (team == 1 ? grp_g[1] : (team == 2 ? grp_g[2] : grp_g[3]));
       const int m0 = mine_pair ? (int)(mg & 0xff) : g0, m1 = mine_pair ? (int)((mg >> 8) & 0xff) : g1;
@@ -1945,6 +1980,10 @@ RCSH_CONTACT_FN uint32_t contact_collide(const ContactTable& tab_, const CheckTa
         const int ta = ga.type, tb = gb.type;
         Shape A = make_shape(ta == 7 ? 0 : ta == 6 ? 1 : 2, pa, Ra, ga.size, hA, ga.vert_num);
         Shape B = make_shape(tb == 7 ? 0 : tb == 6 ? 1 : 2, pb, Rb, gb.size, hB, gb.vert_num);
+        // (a hull of 64 vertices or fewer -- a finger's 49 -- is one trip for a team of 16 already: widening it would only add the step
+        // across the rows.  Every pair of a round has the lead's hull in a place, so a place's span is the same in every lane.)
+        A.span = ga.vert_num > 4 * kTeamLanes ? 1 << slog : kTeamLanes;
+        B.span = gb.vert_num > 4 * kTeamLanes ? 1 << slog : kTeamLanes;
         if (ta == 7) { mulmv(Ra, ga.center, A.center); A.center[0] += pa[0]; A.center[1] += pa[1]; A.center[2] += pa[2]; }
         if (tb == 7) { mulmv(Rb, gb.center, B.center); B.center[0] += pb[0]; B.center[1] += pb[1]; B.center[2] += pb[2]; }
         // a few steps of Gilbert's iteration settle a pair that is clearly apart (links 5 and 7 wrap around the same wrist and pass the
@@ -1970,15 +2009,16 @@ RCSH_CONTACT_FN uint32_t contact_collide(const ContactTable& tab_, const CheckTa
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         if (k >= ngrp) break;  // (wave-uniform)
-        const bool apart_k = __builtin_amdgcn_readlane((int)apart, 16 * k) != 0;
-        const double gap_k = wave_read(gap, 16 * k);
-        int nck = __builtin_amdgcn_readlane(nc, 16 * k);
+        const int lead = k << slog;  // the first lane of pair k's span
+        const bool apart_k = __builtin_amdgcn_readlane((int)apart, lead) != 0;
+        const double gap_k = wave_read(gap, lead);
+        int nck = __builtin_amdgcn_readlane(nc, lead);
         if ((apart_k || nck > 0) && lane == grp_src[k]) {
           const float gf = apart_k ? (float)gap_k * 0.999999f - 1e-6f : -1.0f;  // (-1: in contact -- due in every substep, and marked)
           const int jk = grp_j[k];
           rem[0] = jk == 0 ? gf : rem[0]; rem[1] = jk == 1 ? gf : rem[1]; rem[2] = jk == 2 ? gf : rem[2];
         }
-        if (nck > 0 && lane == 16 * k && nreg + nS < kMaxCon) {
+        if (nck > 0 && lane == lead && nreg + nS < kMaxCon) {
           int c2 = 0;  // what the collision callbacks make of the pair (model.cpp: list_geom_pairs)
           if ((ga.cls | gb.cls) & 1) c2 |= 1;
           if (!((ga.cls & 4) && (gb.cls & 4)) && ((ga.cls | gb.cls) & 16) && !(gb.cls & 8)) c2 |= 2;

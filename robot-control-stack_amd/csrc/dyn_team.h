@@ -96,6 +96,11 @@ __shared__ unsigned long long s_wg_acc[8];  // this workgroup's contact phases: 
   }
 #define TEAM_COUNT(idx) \
   if (blockIdx.x == 0 && threadIdx.x == 0) s_team_cycles[idx] += 1;
+// (hull rounds of the contact phase's narrow stage by the number of pairs refined side by side, 1..4, over ALL workgroups:
+// tools/round_hist.py)
+__device__ unsigned long long g_round_hist[4];
+#define TEAM_ROUND_SHAPE(ngrp) \
+  if ((threadIdx.x & 63) == 0) atomicAdd(&g_round_hist[(ngrp) - 1], 1ull);
 #define TEAM_CLOCK_START()                                        \
   if (blockIdx.x == 0 && threadIdx.x == 0) {                      \
     for (int k_ = 0; k_ < 64; ++k_) s_team_cycles[k_] = 0;        \
@@ -108,6 +113,7 @@ __shared__ unsigned long long s_wg_acc[8];  // this workgroup's contact phases: 
 #else
 #define TEAM_MARK(idx)
 #define TEAM_COUNT(idx)
+#define TEAM_ROUND_SHAPE(ngrp)
 #define TEAM_CLOCK_START()
 #define TEAM_CLOCK_FLUSH()
 #endif

@@ -247,7 +247,9 @@ Params make_params(rcsh_sim* s) {
   // Gilbert fallback, 4 no slack record (timing experiments, check_team.h); bit 5 sends every coupled environment of a box-less scene to the
   // wide solve (contact_wide.h) whatever its contact count, not only those with more than kDenseCon contacts (contact_dense.h; the tests
   // of the wide solve's math on few contacts, tests/test_gpu_contact_wide.py); bit 6 takes the pairs-only shortcut out of the contact phase's
-  // collision pass (contact_team.h: contact_collide; tests/test_gpu_quiet_escalated.py compares the two forms).  Read on every launch.
+  // collision pass (contact_team.h: contact_collide; tests/test_gpu_quiet_escalated.py compares the two forms); bit 7 keeps every hull round of
+  // that pass on teams of 16 lanes, where a lone pair takes the wavefront and two pairs half of it each (tests/test_gpu_wide_support.py
+  // compares the two forms), bit 8 only the rounds of two pairs (a timing experiment).  Read on every launch.
   return P;
 }
 
@@ -2985,6 +2987,10 @@ extern "C" int rcsh_debug_team_cycles96(unsigned long long* out96, int clear_max
     hipMemcpyToSymbol(HIP_SYMBOL(g_team_cycles), &z, sizeof(z), sizeof(z) * 68);
   }
   return 0;
+}
+extern "C" int rcsh_debug_round_hist(unsigned long long* out4) {  // hull rounds with 1, 2, 3, 4 pairs since the library was loaded
+  hipDeviceSynchronize();
+  return hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_round_hist), sizeof(unsigned long long) * 4) == hipSuccess ? 0 : 1;
 }
 extern "C" int rcsh_debug_team_cycles64(unsigned long long* out64) {
   hipDeviceSynchronize();
