@@ -263,6 +263,45 @@ int rcsh_motion_query(rcsh_sim* sim, const double* q_from, const double* q_to, c
 int rcsh_motion_query_dev(rcsh_sim* sim, const double* q_from_dev, const double* q_to_dev, const double* free_qpos_dev, int32_t m,
                           int32_t kinds, double resolution, int32_t* result_dev, double* t_contact_dev);
 
+/* ---- clearance queries: how far, between which geoms, and which way to move (csrc/clearance_team.h).
+ * rcsh_clearance_pairs lists the pairs a clearance query covers for `kinds`, as mjModel geom ids, each pair in MuJoCo's order within
+ * a contact, in a fixed order: (1) the floor pairs, in geom order; (2) the self pairs, in the order of the end-of-launch check's
+ * table; (3) the free body's pairs, in geom order.  That is exactly the set the point query tests: pairs the tables drop (a
+ * parent-child pair across the first hinge) are not in it.  geom_ids [capacity][2]; capacity may be 0 to read *count alone; a robot
+ * without collision geoms has count 0.
+ * rcsh_clearance_query: q, free_qpos, kinds, RCSH_ERR_MODEL and RCSH_ERR_ARG as rcsh_collision_query; no per-environment state is read
+ * or written; the handle's stream.  pair_mask [count] bytes, indexed by the list for the same `kinds`: 0 skips the pair; NULL: every
+ * pair.  d_max > 0 (+inf allowed; NaN or <= 0: RCSH_ERR_ARG): pairs farther apart than d_max are not looked for.  Every output but
+ * `distance` may be NULL.  Per row:
+ *   status [M]  0 apart: distance [M] is the smallest Euclidean distance over the selected pairs, within 1e-9 m;
+ *               1 nothing within d_max: distance == d_max, pair -1 -1, witness and grad zeros;
+ *               2 in contact (some selected pair penetrates by more than 1e-9 m, the point query's predicate): distance is minus the
+ *                 depth of the deepest penetrating pair -- the depth of the contact pass's narrow phase (MPR; the lowest point against
+ *                 the floor; the box-box collider's depth for two boxes);
+ *               3 not converged (the distance iteration met its cap of 64 support queries): distance is the proven lower bound, never
+ *                 more than the truth; pair and witness are the iteration's last;
+ *   pair [M][2]     the pair that attains `distance` (ties: the lowest list index);
+ *   witness [M][6]  world points wa on the first geom and wb on the second, in the list's order (a capsule's is the point of its
+ *                   core segment: |wb - wa| minus the capsules' radii is the distance); status 2: the contact position
+ *                   +- half the depth along the contact normal (wa = pos + n depth / 2, wb = pos - n depth / 2);
+ *   grad [M][nl]    d(distance)/dq_j with the witnesses held fixed on their geoms: n . (v_b,j - v_a,j), n = (wb - wa) / |wb - wa|
+ *                   (status 2: the contact normal, from the first geom to the second), v_x,j = axis_j x (w_x - anchor_j) for a hinge
+ *                   among the ancestors of x's link, axis_j for a slide, 0 otherwise (geoms welded to the world, the floor and the
+ *                   free body do not move).
+ * rcsh_env_clearance asks the same once per environment (M = n_envs): the row is the environment's own chain configuration (arm
+ * joints and finger slides, what the collision guard reads) and, with bit 2 of `kinds` in a scene with a free body, the body at the
+ * environment's own pose.  It writes nothing but its outputs. */
+int rcsh_clearance_pairs(rcsh_sim* sim, int32_t kinds, int32_t* geom_ids, int32_t capacity, int32_t* count);
+int rcsh_clearance_query(rcsh_sim* sim, const double* q, const double* free_qpos, int32_t m, int32_t kinds, const uint8_t* pair_mask,
+                         double d_max, double* distance, uint8_t* status, int32_t* pair, double* witness, double* grad);
+int rcsh_clearance_query_dev(rcsh_sim* sim, const double* q_dev, const double* free_qpos_dev, int32_t m, int32_t kinds,
+                             const uint8_t* pair_mask_dev, double d_max, double* distance_dev, uint8_t* status_dev, int32_t* pair_dev,
+                             double* witness_dev, double* grad_dev);
+int rcsh_env_clearance(rcsh_sim* sim, int32_t kinds, const uint8_t* pair_mask, double d_max, double* distance, uint8_t* status,
+                       int32_t* pair, double* witness, double* grad);
+int rcsh_env_clearance_dev(rcsh_sim* sim, int32_t kinds, const uint8_t* pair_mask_dev, double d_max, double* distance_dev,
+                           uint8_t* status_dev, int32_t* pair_dev, double* witness_dev, double* grad_dev);
+
 /* SimGripper(sim, cfg) -- rcs.cpp:508-515, SimGripper.cpp:13-39 */
 int rcsh_sim_add_gripper(rcsh_sim* sim, const rcsh_gripper_desc* gripper);
 /* Gripper.set_normalized_width -- rcs.cpp:383-384, SimGripper.cpp:79-92 (RCSH_ERR_ARG outside [0,1] / force<0) */

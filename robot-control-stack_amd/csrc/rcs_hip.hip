@@ -20,6 +20,7 @@
 #include "sim_kernels.h"
 #include "render.h"
 #include "query_team.h"
+#include "clearance_team.h"
 #include "guard_team.h"
 #include "episode_team.h"
 
@@ -1298,6 +1299,169 @@ int rcsh_motion_query_dev(rcsh_sim* s, const double* q_from_dev, const double* q
   if (m == 0) return RCSH_OK;
   if (!q_from_dev || !q_to_dev || !result_dev || !t_contact_dev) return fail(RCSH_ERR_ARG, "null argument");
   return motion_query_dev(s, q_from_dev, q_to_dev, free_qpos_dev, m, kinds, resolution, result_dev, t_contact_dev);
+}
+
+// ---- clearance queries (csrc/clearance_team.h)
+namespace {
+// The pairs a clearance query covers for `kinds`, in the list's order: the floor pairs in geom order, the check's table, the free
+// body's pairs in geom order -- what query_config tests.  floor_bits / box_bits: the table geoms behind the first and the last group.
+struct ClearList {
+  std::vector<int32_t> ids;  // [count][2] mjModel geom ids, MuJoCo's order within a contact
+  uint32_t floor_bits = 0, box_bits = 0;
+  int count() const { return (int)ids.size() / 2; }
+};
+void clearance_list(rcsh_sim* s, int32_t kinds, ClearList& L) {
+  const int box_geom = s->hm.ngeom;
+  for (size_t g = 0; g < s->cgeoms.size() && g < 32; ++g) {
+    const ContactGeom& cg = s->cgeoms[g];
+    const bool solid = cg.type != 7 || cg.vert_num > 0;
+    if (s->cp.has_plane && cg.plane_ok && cg.link >= 0 && solid) L.floor_bits |= 1u << g;
+    const int gid = cg.geom_id;
+    if (s->box.present && solid && ((s->hm.geom_contype[gid] & 1) || (s->hm.geom_conaffinity[gid] & 1))) L.box_bits |= 1u << g;
+  }
+  if (kinds & kQueryFloor)
+    for (size_t g = 0; g < s->cgeoms.size() && g < 32; ++g)
+      if ((L.floor_bits >> g) & 1u) { L.ids.push_back(s->cp.plane_geom); L.ids.push_back(s->cgeoms[g].geom_id); }
+  if (kinds & kQuerySelf)
+    for (const SelfPair& p : s->tables.chk_pairs) { L.ids.push_back(s->cgeoms[p.g0].geom_id); L.ids.push_back(s->cgeoms[p.g1].geom_id); }
+  if (kinds & kQueryBox)
+    for (size_t g = 0; g < s->cgeoms.size() && g < 32; ++g)
+      if ((L.box_bits >> g) & 1u) {
+        const bool hull = s->cgeoms[g].type == 7;  // (query_pair_ids: the free box before a hull, after a capsule or a robot box)
+        L.ids.push_back(hull ? box_geom : s->cgeoms[g].geom_id);
+        L.ids.push_back(hull ? s->cgeoms[g].geom_id : box_geom);
+      }
+}
+int clearance_check(rcsh_sim* s, int32_t m, int32_t kinds, const double* free_qpos, double d_max) {
+  int rc = query_check(s, m, kinds, free_qpos);
+  if (rc) return rc;
+  if (!(d_max > 0.0)) return fail(RCSH_ERR_ARG, "d_max must be greater than 0 (+inf is allowed)");
+  return RCSH_OK;
+}
+struct ClearOut { double* distance; uint8_t* status; int32_t* pair; double* witness; double* grad; };
+// device pointers in; S non-null: the environments' own rows (m = n_envs; box_field as GuardArgs::box_field)
+int clearance_dev(rcsh_sim* s, const double* q, const double* free_qpos, int32_t m, int32_t kinds, const uint8_t* pair_mask, double d_max,
+                  const ClearOut& o, const double* S, int box_field) {
+  if (s->cgeoms.empty()) {
+    hipLaunchKernelGGL(k_clearance_fill, dim3((m + 63) / 64), dim3(64), 0, s->stream, o.distance, o.status, o.pair, o.witness, o.grad, d_max, m, s->nl);
+    HIP_TRY(hipGetLastError());
+    return RCSH_OK;
+  }
+  ClearList L;
+  clearance_list(s, kinds, L);
+  ClearArgs A{};
+  A.Q = query_args(s, m, kinds);
+  A.Q.q0 = q; A.Q.free_qpos = free_qpos;
+  A.floor_bits = L.floor_bits; A.box_bits = L.box_bits;
+  A.pair_mask = pair_mask; A.d_max = d_max;
+  A.distance = o.distance; A.status = o.status; A.pair = o.pair; A.witness = o.witness; A.grad = o.grad;
+  A.S = S; A.qpos_field = field_of(s, "qpos"); A.box_field = box_field;
+  hipError_t err = hipSuccess;
+  const bool ok = dispatch_topology(s->narm, s->grip, [&](auto topo) {
+    using T = decltype(topo);
+    hipLaunchKernelGGL(k_clearance_query<T>, dim3((m + 3) / 4), dim3(64), 0, s->stream, A);
+    err = hipGetLastError();
+  });
+  if (!ok) return fail(RCSH_ERR_MODEL, "no kernel instantiated for this archetype");
+  if (err != hipSuccess) return fail(RCSH_ERR_DEVICE, std::string("clearance query launch: ") + hipGetErrorString(err));
+  return RCSH_OK;
+}
+// Device staging of the host-pointer clearance forms, cut out of d_query (offsets in bytes; every slice 8-byte aligned):
+// [q | free_qpos | pair_mask | distance | witness | grad | pair | status]
+struct ClearLayout { size_t q, free_qpos, mask, distance, witness, grad, pair, status, total; };
+ClearLayout clear_layout(size_t n, size_t nl, bool rows, bool free_body, size_t nmask) {
+  ClearLayout c{};
+  c.q = 0;
+  c.free_qpos = c.q + (rows ? 8 * n * nl : 0);
+  c.mask = c.free_qpos + (free_body ? 8 * n * 7 : 0);
+  c.distance = align8(c.mask + nmask);
+  c.witness = c.distance + 8 * n;
+  c.grad = c.witness + 8 * n * 6;
+  c.pair = c.grad + 8 * n * nl;
+  c.status = c.pair + 8 * n;
+  c.total = align8(c.status + n);
+  return c;
+}
+// the host form of both queries: q null: the environments' own rows
+int clearance_host(rcsh_sim* s, const double* q, const double* free_qpos, int32_t m, int32_t kinds, const uint8_t* pair_mask, double d_max,
+                   double* distance, uint8_t* status, int32_t* pair, double* witness, double* grad, const double* S, int box_field) {
+  const size_t nl = (size_t)s->nl, n = (size_t)m;
+  ClearList L;
+  if (pair_mask) clearance_list(s, kinds, L);
+  const size_t nmask = (size_t)L.count();
+  const ClearLayout c = clear_layout(n, nl, q != nullptr, free_qpos != nullptr, nmask);
+  int rc = grow_device(s, s->d_query, c.total);
+  if (rc) return rc;
+  char* d = static_cast<char*>(s->d_query.p.get());
+  if (q) HIP_TRY(hipMemcpyAsync(d + c.q, q, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
+  if (free_qpos) HIP_TRY(hipMemcpyAsync(d + c.free_qpos, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
+  if (nmask) HIP_TRY(hipMemcpyAsync(d + c.mask, pair_mask, nmask, hipMemcpyHostToDevice, s->stream));
+  const ClearOut o{reinterpret_cast<double*>(d + c.distance), reinterpret_cast<uint8_t*>(d + c.status), reinterpret_cast<int32_t*>(d + c.pair),
+                   reinterpret_cast<double*>(d + c.witness), reinterpret_cast<double*>(d + c.grad)};
+  rc = clearance_dev(s, q ? reinterpret_cast<const double*>(d + c.q) : nullptr, free_qpos ? reinterpret_cast<const double*>(d + c.free_qpos) : nullptr,
+                     m, kinds, nmask ? reinterpret_cast<const uint8_t*>(d + c.mask) : nullptr, d_max, o, S, box_field);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(distance, o.distance, 8 * n, hipMemcpyDeviceToHost, s->stream));
+  if (status) HIP_TRY(hipMemcpyAsync(status, o.status, n, hipMemcpyDeviceToHost, s->stream));
+  if (pair) HIP_TRY(hipMemcpyAsync(pair, o.pair, 8 * n, hipMemcpyDeviceToHost, s->stream));
+  if (witness) HIP_TRY(hipMemcpyAsync(witness, o.witness, 8 * n * 6, hipMemcpyDeviceToHost, s->stream));
+  if (grad) HIP_TRY(hipMemcpyAsync(grad, o.grad, 8 * n * nl, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RCSH_OK;
+}
+// the free body of the environments' own rows: tested when the scene has one and `kinds` asks for it
+int env_clearance_box_field(rcsh_sim* s, int32_t kinds) { return (kinds & kQueryBox) && s->box.present ? field_of(s, "box") + kBoxQ : -1; }
+}  // namespace
+
+int rcsh_clearance_pairs(rcsh_sim* s, int32_t kinds, int32_t* geom_ids, int32_t capacity, int32_t* count) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (!count || capacity < 0 || (capacity > 0 && !geom_ids)) return fail(RCSH_ERR_ARG, "null argument");
+  int rc = query_check(s, 0, kinds, nullptr);
+  if (rc) return rc;
+  ClearList L;
+  clearance_list(s, kinds, L);
+  *count = L.count();
+  for (int i = 0; i < L.count() && i < capacity; ++i) { geom_ids[2 * i] = L.ids[2 * i]; geom_ids[2 * i + 1] = L.ids[2 * i + 1]; }
+  return RCSH_OK;
+}
+int rcsh_clearance_query(rcsh_sim* s, const double* q, const double* free_qpos, int32_t m, int32_t kinds, const uint8_t* pair_mask, double d_max,
+                         double* distance, uint8_t* status, int32_t* pair, double* witness, double* grad) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  int rc = clearance_check(s, m, kinds, free_qpos, d_max);
+  if (rc) return rc;
+  if (m == 0) return RCSH_OK;
+  if (!q || !distance) return fail(RCSH_ERR_ARG, "null argument");
+  if ((rc = query_finite(q, (size_t)m * s->nl, "q"))) return rc;
+  if (free_qpos && (rc = query_finite(free_qpos, (size_t)m * 7, "free_qpos"))) return rc;
+  return clearance_host(s, q, free_qpos, m, kinds, pair_mask, d_max, distance, status, pair, witness, grad, nullptr, -1);
+}
+int rcsh_clearance_query_dev(rcsh_sim* s, const double* q_dev, const double* free_qpos_dev, int32_t m, int32_t kinds, const uint8_t* pair_mask_dev,
+                             double d_max, double* distance_dev, uint8_t* status_dev, int32_t* pair_dev, double* witness_dev, double* grad_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  int rc = clearance_check(s, m, kinds, free_qpos_dev, d_max);
+  if (rc) return rc;
+  if (m == 0) return RCSH_OK;
+  if (!q_dev || !distance_dev) return fail(RCSH_ERR_ARG, "null argument");
+  return clearance_dev(s, q_dev, free_qpos_dev, m, kinds, pair_mask_dev, d_max, ClearOut{distance_dev, status_dev, pair_dev, witness_dev, grad_dev},
+                       nullptr, -1);
+}
+int rcsh_env_clearance(rcsh_sim* s, int32_t kinds, const uint8_t* pair_mask, double d_max, double* distance, uint8_t* status, int32_t* pair,
+                       double* witness, double* grad) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  int rc = clearance_check(s, s->n, kinds, nullptr, d_max);
+  if (rc) return rc;
+  if (!distance) return fail(RCSH_ERR_ARG, "null argument");
+  return clearance_host(s, nullptr, nullptr, s->n, kinds, pair_mask, d_max, distance, status, pair, witness, grad, s->S.get(),
+                        env_clearance_box_field(s, kinds));
+}
+int rcsh_env_clearance_dev(rcsh_sim* s, int32_t kinds, const uint8_t* pair_mask_dev, double d_max, double* distance_dev, uint8_t* status_dev,
+                           int32_t* pair_dev, double* witness_dev, double* grad_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  int rc = clearance_check(s, s->n, kinds, nullptr, d_max);
+  if (rc) return rc;
+  if (!distance_dev) return fail(RCSH_ERR_ARG, "null argument");
+  return clearance_dev(s, nullptr, nullptr, s->n, kinds, pair_mask_dev, d_max, ClearOut{distance_dev, status_dev, pair_dev, witness_dev, grad_dev},
+                       s->S.get(), env_clearance_box_field(s, kinds));
 }
 
 int rcsh_robot_get_state(rcsh_sim* s, uint8_t* ik_success, uint8_t* collision, uint8_t* is_moving, uint8_t* is_arrived,

@@ -202,6 +202,7 @@ EXPORTS = (
     "rcsh_sim_contact_escalated",
     "rcsh_sim_contact_overflow",
     "rcsh_collision_query", "rcsh_collision_query_dev", "rcsh_motion_query", "rcsh_motion_query_dev",
+    "rcsh_clearance_pairs", "rcsh_clearance_query", "rcsh_clearance_query_dev", "rcsh_env_clearance", "rcsh_env_clearance_dev",
     "rcsh_env_configure_guard", "rcsh_env_guard_peek", "rcsh_env_guard_peek_dev", "rcsh_env_guard_last", "rcsh_env_guard_last_dev",
     "rcsh_env_configure_autoreset", "rcsh_env_autoreset_record_dev", "rcsh_env_autoreset_last", "rcsh_autoreset_draw",
 )
@@ -285,6 +286,11 @@ def load() -> C.CDLL:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     for fn in (L.rcsh_motion_query, L.rcsh_motion_query_dev):
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
+    L.rcsh_clearance_pairs.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _I32P]
+    for fn in (L.rcsh_clearance_query, L.rcsh_clearance_query_dev):
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_double] + [C.c_void_p] * 5
+    for fn in (L.rcsh_env_clearance, L.rcsh_env_clearance_dev):
+        fn.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double] + [C.c_void_p] * 5
     L.rcsh_env_configure_guard.argtypes = [C.c_void_p, C.POINTER(GuardDesc)]
     for fn in (L.rcsh_env_guard_peek, L.rcsh_env_guard_peek_dev):
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -159,6 +159,39 @@ class VecSimEnv:
         _lib.check(self._L.rcsh_env_guard_last_dev(self.sim._h, C.byref(r), C.byref(t), C.byref(b)))
         return int(b.value), int(r.value), int(t.value)
 
+    # ---- clearance (csrc/clearance_team.h): on demand, not part of step
+    def clearance(self, kinds: int | None = None, pair_mask=None, d_max: float = np.inf):
+        """Every environment's distance to the nearest obstacle where it is now: its own arm joints and finger slides and -- in a
+        scene with a free body, ``kinds`` bit 2 -- the body at its own pose.  Arguments and the returned ``(distance [N], status [N],
+        pair [N, 2], witness [N, 6], grad [N, nl])`` as :meth:`rcs_amd.sim.SimRobot.check_clearance` (``kinds`` None: every kind;
+        ``pair_mask`` indexed by ``robot.clearance_pairs(kinds)``).  Reads the state, writes none of it."""
+        n = self.n_envs
+        kinds = sim.SimRobot.COLLISION_ALL if kinds is None else int(kinds)
+        mask = None
+        if pair_mask is not None:
+            mask = np.ascontiguousarray(pair_mask, dtype=np.uint8).reshape(-1)
+            count = C.c_int32(0)
+            _lib.check(self._L.rcsh_clearance_pairs(self.sim._h, kinds, None, 0, C.byref(count)))
+            if mask.shape[0] != count.value:
+                raise ValueError(f"pair_mask has {mask.shape[0]} entries, the pair list for kinds={kinds} has {count.value}")
+        dist = np.zeros(n)
+        status = np.zeros(n, dtype=np.uint8)
+        pair = np.full((n, 2), -1, dtype=np.int32)
+        wit = np.zeros((n, 6))
+        grad = np.zeros((n, int(self.sim.model.nq)))
+        _lib.check(self._L.rcsh_env_clearance(self.sim._h, kinds, _lib.ptr(mask), float(d_max), _lib.ptr(dist), _lib.ptr(status),
+                                              _lib.ptr(pair), _lib.ptr(wit), _lib.ptr(grad)))
+        return dist, status, pair, wit, grad
+
+    def clearance_dev(self, distance_dev: int, status_dev: int = 0, pair_dev: int = 0, witness_dev: int = 0, grad_dev: int = 0,
+                      kinds: int | None = None, pair_mask_dev: int = 0, d_max: float = np.inf) -> None:
+        """:meth:`clearance` into device buffers (addresses; 0: not wanted -- ``distance_dev`` is required), enqueued on the Sim's
+        stream without a synchronisation.  ``pair_mask_dev``: device address of the mask bytes, 0 for every pair."""
+        kinds = sim.SimRobot.COLLISION_ALL if kinds is None else int(kinds)
+        p = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        _lib.check(self._L.rcsh_env_clearance_dev(self.sim._h, kinds, p(pair_mask_dev), float(d_max), p(distance_dev), p(status_dev),
+                                                  p(pair_dev), p(witness_dev), p(grad_dev)))
+
     def _guard_info(self, i: dict[str, Any]):
         """info["guard_*"] of a guarded step; returns ``blocked`` where it truncates (else None)."""
         if not self.guard_enabled:

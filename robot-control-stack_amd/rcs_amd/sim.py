@@ -564,6 +564,65 @@ class SimRobot:
                                              _lib.ptr(res), _lib.ptr(tc)))
         return res, tc
 
+    def clearance_pairs(self, kinds: int = COLLISION_ALL) -> np.ndarray:
+        """[count, 2] int32: the geom pairs a clearance query covers for ``kinds`` (mjModel geom ids, MuJoCo's order within a contact),
+        in the order ``pair_mask`` is indexed by: the floor pairs in geom order, the self pairs in the order of the contact check's
+        table, the free body's pairs in geom order.  Exactly what ``check_collision`` tests."""
+        count = C.c_int32(0)
+        _lib.check(self._L.rcsh_clearance_pairs(self.sim._h, int(kinds), None, 0, C.byref(count)))
+        out = np.zeros((count.value, 2), dtype=np.int32)
+        if count.value:
+            _lib.check(self._L.rcsh_clearance_pairs(self.sim._h, int(kinds), _lib.ptr(out), count.value, C.byref(count)))
+        return out
+
+    def clearance_mask(self, kinds: int = COLLISION_ALL, ignore=(), ignore_finger_pairs: bool = True) -> np.ndarray:
+        """A ``pair_mask`` for ``check_clearance``: 1 for every pair of ``clearance_pairs(kinds)`` except those in ``ignore``
+        (geom-id pairs, either order) and -- by default -- the pairs of two gripper-finger geoms: the two fingers' pads are a few
+        millimetres apart whenever the hand is nearly shut, and would be the nearest pair of almost every row."""
+        pairs = self.clearance_pairs(kinds)
+        drop = {frozenset((int(a), int(b))) for a, b in ignore}
+        fingers = set()
+        if ignore_finger_pairs:
+            # (a finger geom: one on the body of a joint behind the arm's -- the finger slides)
+            arr = self.sim.model.arrays
+            bodies = {int(b) for b in np.asarray(arr["jnt_bodyid"])[self.dof:]}
+            fingers = {g for g, b in enumerate(np.asarray(arr["geom_bodyid"])) if int(b) in bodies}
+        mask = np.ones(len(pairs), dtype=np.uint8)
+        for i, (a, b) in enumerate(pairs):
+            if frozenset((int(a), int(b))) in drop or (int(a) in fingers and int(b) in fingers):
+                mask[i] = 0
+        return mask
+
+    def check_clearance(self, q, free_qpos=None, kinds: int = COLLISION_ALL, pair_mask=None, d_max: float = np.inf, finger_qpos=None,
+                        want_grad: bool = True):
+        """How far is the robot from the nearest obstacle at each configuration, between which geoms, and which way does the
+        distance grow?  Rows, ``free_qpos``, ``kinds`` and ``finger_qpos`` as ``check_collision``; ``pair_mask``: uint8
+        [len(clearance_pairs(kinds))], 0 skips a pair (``clearance_mask`` builds one); ``d_max``: pairs farther apart are not
+        looked for.
+
+        Returns ``(distance [M], status [M] uint8, pair [M, 2] int32, witness [M, 6], grad [M, nl] or None)``: status 0 apart --
+        distance is the smallest distance over the selected pairs (within 1e-9 m), 1 nothing within d_max (distance == d_max, pair
+        -1 -1), 2 in contact (distance is minus the deepest pair's penetration depth), 3 the distance iteration did not converge
+        (distance is a proven lower bound).  witness: the closest points on the pair's first and second geom (world frame); grad:
+        d(distance)/dq with the witnesses held fixed on their geoms (include/rcs_hip.h, rcsh_clearance_query)."""
+        rows = self._query_rows(q, finger_qpos, "q")
+        m = rows.shape[0]
+        fq = self._free_rows(free_qpos, m)
+        mask = None
+        if pair_mask is not None:
+            mask = np.ascontiguousarray(pair_mask, dtype=np.uint8).reshape(-1)
+            count = len(self.clearance_pairs(kinds))
+            if mask.shape[0] != count:
+                raise ValueError(f"pair_mask has {mask.shape[0]} entries, clearance_pairs({kinds}) lists {count}")
+        dist = np.zeros(m)
+        status = np.zeros(m, dtype=np.uint8)
+        pair = np.full((m, 2), -1, dtype=np.int32)
+        wit = np.zeros((m, 6))
+        grad = np.zeros((m, rows.shape[1])) if want_grad else None
+        _lib.check(self._L.rcsh_clearance_query(self.sim._h, _lib.ptr(rows), _lib.ptr(fq), m, int(kinds), _lib.ptr(mask), float(d_max),
+                                                _lib.ptr(dist), _lib.ptr(status), _lib.ptr(pair), _lib.ptr(wit), _lib.ptr(grad)))
+        return dist, status, pair, wit, grad
+
 
 @dataclass
 class SimGripperConfig:  # reference src/sim/SimGripper.h:15-45
