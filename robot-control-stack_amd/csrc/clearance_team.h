@@ -7,9 +7,11 @@
 // point against the floor).  The pairs are the point query's: the floor pairs, the check's table, the free body's pairs.
 //
 // One row per TEAM of 16 lanes (team.h), four per wavefront, as k_collision_query.  Per row:
-//  1. link frames, world boxes and the free body's frame as query_config computes them;
+//  1. link frames, world boxes and the free body's frame as query_config computes them (query_box_frame and, for an environment's own
+//     row, query_env_row are query_team.h's; the frames, the broad levels and the narrow phase's setup are this kernel's own text: calling
+//     query_config's made this kernel slower than it was);
 //  2. LOWER BOUNDS of every selected pair's distance, a lane per pair (t + 16 j) and geom (t + 16 u): bounding spheres, then the
-//     oriented boxes' face separation.  A pair the boxes do not prove apart is bounded by -inf: it may penetrate.  A pair the caller's
+//     oriented boxes' face separation (as query_config has them).  A pair the boxes do not prove apart is bounded by -inf: it may penetrate.  A pair the caller's
 //     mask leaves out is bounded by +inf.  Floor pairs are exact at this level, with their witness;
 //  3. best first: the team takes the pending pair of the smallest bound (ties: the lowest key) and computes its exact distance on its
 //     16 lanes (gjk_distance), until the smallest pending bound is no smaller than the best value found or than d_max;
@@ -26,9 +28,7 @@ constexpr int kGjkCap = 64;
 constexpr double kGjkBand = 1e-10;  // stop: |x| minus the proven lower bound at most this
 
 struct ClearArgs {
-  QueryArgs Q;               // tables, kinds, m, q0, free_qpos (the outputs of the collision queries are unused)
-  uint32_t floor_bits;       // bit g: (floor, geom g) is a pair of the list (rcsh_clearance_pairs)
-  uint32_t box_bits;         // bit g: (geom g, free body) is
+  QueryArgs Q;               // tables, kinds, the pair set's bits, m, q0, free_qpos (the outputs of the collision queries are unused)
   const uint8_t* pair_mask;  // [count], in the list's order for Q.kinds; null: every pair
   double d_max;
   double* distance;          // [m]
@@ -205,16 +205,15 @@ RCSH_D void clear_offer(ClearBest& B, double value, int key, int la, int lb, boo
   for (int k = 0; k < 3; ++k) { B.wa[k] = t ? wa[k] : B.wa[k]; B.wb[k] = t ? wb[k] : B.wb[k]; B.n[k] = t ? n[k] : B.n[k]; }
 }
 
-// where a key stands in the list of rcsh_clearance_pairs for the row's kinds: the floor pairs, the table, the free body's pairs
-RCSH_D int clear_list_index(const ClearArgs& A, int key) {
+// where a key stands in the list of rcsh_clearance_pairs for the row's kinds (build_query_pairs): the floor pairs, the table, the free
+// body's pairs
+RCSH_D int clear_list_index(const QueryArgs& Q, int key) {
   const int kind = key >> 16, i = key & 0xffff;
-  const int nfloor = (A.Q.kinds & kQueryFloor) ? __popc(A.floor_bits) : 0;
-  const int nself = (A.Q.kinds & kQuerySelf) ? A.Q.ck.npair : 0;
-  if (kind == 0) return __popc(A.floor_bits & ((1u << i) - 1u));
-  if (kind == 1) return nfloor + i;
-  return nfloor + nself + __popc(A.box_bits & ((1u << i) - 1u));
+  if (kind == 0) return __popc(Q.floor_bits & ((1u << i) - 1u));
+  if (kind == 1) return __popc(Q.floor_bits) + i;
+  return __popc(Q.floor_bits) + ((Q.kinds & kQuerySelf) ? Q.ck.npair : 0) + __popc(Q.box_bits & ((1u << i) - 1u));
 }
-RCSH_D bool clear_selected(const ClearArgs& A, int key) { return !A.pair_mask || A.pair_mask[clear_list_index(A, key)] != 0; }
+RCSH_D bool clear_selected(const ClearArgs& A, int key) { return !A.pair_mask || A.pair_mask[clear_list_index(A.Q, key)] != 0; }
 
 // Clearance query: one row per team.
 template <class T>
@@ -227,27 +226,22 @@ __global__ void __launch_bounds__(64) k_clearance_query(ClearArgs A) {
   const QueryArgs& Q = A.Q;
   const int e = blockIdx.x * kTeams + team;
   const bool live = e < Q.m;
-  const size_t ec = live ? e : 0;
   const bool valid = t < NL;
-  const int tl = valid ? t : NL - 1;
   const CheckTable& ck = Q.ck;
   const int npair = ck.npair, ngeom = ck.ngeom;
   // ---- the row: the caller's, or the environment's own chain and free body
-  double q = 0.0, fq[7];
+  double q, fq[7];
   bool use_box;
   if (A.S) {
-    if (live && valid) q = A.S[(size_t)(A.qpos_field + t) * Q.m + ec];
-    use_box = live && A.box_field >= 0;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) fq[k] = use_box ? A.S[(size_t)(A.box_field + k) * Q.m + ec] : (k == 3 ? 1.0 : 0.0);
+    use_box = query_env_row(A.S, Q.m, e, live, valid, A.qpos_field, A.box_field, q, fq);
   } else {
-    if (live && valid) q = Q.q0[ec * NL + t];
+    q = live && valid ? Q.q0[(size_t)e * NL + t] : 0.0;
     use_box = query_free_pose(Q, e, live, fq);
   }
   // ---- link frames, world boxes, the free body's frame (query_config's prologue)
   {
     KinK kk;
-    kk.load(Q.links[tl]);
+    kk.load(Q.links[valid ? t : NL - 1]);
     double R[9], p[3];
     link_local_frame(kk, q, R, p);
     scan_frames<T>(R, p);
@@ -274,16 +268,8 @@ __global__ void __launch_bounds__(64) k_clearance_query(ClearArgs A) {
     }
   }
   stage_fence();
-  double bp[3] = {0, 0, 0}, bR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  if (use_box) {
-    const double qn = sqrt(fq[3] * fq[3] + fq[4] * fq[4] + fq[5] * fq[5] + fq[6] * fq[6]);
-    const bool deg = !(qn >= 1e-15);
-    const double w = deg ? 1.0 : fq[3] / qn, x = deg ? 0.0 : fq[4] / qn, y = deg ? 0.0 : fq[5] / qn, z = deg ? 0.0 : fq[6] / qn;
-    bR[0] = 1 - 2 * (y * y + z * z); bR[1] = 2 * (x * y - w * z);     bR[2] = 2 * (x * z + w * y);
-    bR[3] = 2 * (x * y + w * z);     bR[4] = 1 - 2 * (x * x + z * z); bR[5] = 2 * (y * z - w * x);
-    bR[6] = 2 * (x * z - w * y);     bR[7] = 2 * (y * z + w * x);     bR[8] = 1 - 2 * (x * x + y * y);
-    bp[0] = fq[0]; bp[1] = fq[1]; bp[2] = fq[2];
-  }
+  double bp[3], bR[9];
+  query_box_frame(fq, use_box, bp, bR);
   const double* bs = Q.box_size;
   const double d_max = A.d_max;
   // ---- the floor (exact: the lane's candidate with its witness) and the bounds of the free body's pairs: lane t takes geoms t, t + 16
@@ -298,7 +284,7 @@ __global__ void __launch_bounds__(64) k_clearance_query(ClearArgs A) {
     const ContactGeom& cg = Q.geoms[g];
     double gR[9], gpos[3];
     query_geom_world(cg, F, gR, gpos);
-    if ((Q.kinds & kQueryFloor) && ((A.floor_bits >> g) & 1u) && clear_selected(A, (0 << 16) | g)) {
+    if (((Q.floor_bits >> g) & 1u) && clear_selected(A, (0 << 16) | g)) {
       const double* n = Q.plane_n;
       double nl[3], wl[3] = {0, 0, 0}, low, rad = 0.0;
       mulTv(gR, n, nl);
@@ -339,7 +325,7 @@ __global__ void __launch_bounds__(64) k_clearance_query(ClearArgs A) {
         for (int k = 0; k < 3; ++k) fl_w[k] = ww[k] + gpos[k];  // (a capsule: the end of its core segment)
       }
     }
-    if (use_box && (Q.kinds & kQueryBox) && ((A.box_bits >> g) & 1u) && clear_selected(A, (2 << 16) | g)) {
+    if (use_box && ((Q.box_bits >> g) & 1u) && clear_selected(A, (2 << 16) | g)) {
       double hc[3], hh[3], oc[3];
       geom_obb(cg, hc, hh);
       mulmv(gR, hc, oc);

@@ -62,6 +62,7 @@ struct CheckEntry {
 struct CheckGeom {
   double c[3], rot[9];
 };
+constexpr int kQueryFloor = 1, kQuerySelf = 2, kQueryBox = 4, kQueryKinds = 7;  // the `kinds` mask of the queries (query_team.h)
 constexpr int kSlackFloor = kMaxCheckPairs + 24;  // ... then the geoms' remaining heights above the floor
 constexpr int kSlackLink = kSlackFloor + 32;      // ... then, per LINK, what is left of its sample points' height above the floor (the lean launch's check)
 constexpr int kSlackStride = kSlackLink + 16;     // floats per environment: the pairs' remaining gaps, then the joints seen last (12 doubles), ...

@@ -6,7 +6,8 @@
 // passes when the straight joint-space motion from where the arm IS to where the action SENDS it is proven free.
 //
 // One environment per TEAM of 16 lanes, four per wavefront, as k_motion_query -- but the segment is the environment's own:
-//  * start: the chain configuration the stepping kernels will load (Lay::QPOS: arm joints and finger slides);
+//  * start: the chain configuration the stepping kernels will load (Lay::QPOS: arm joints and finger slides), read by
+//    query_env_row (query_team.h) as the env form of the clearance query reads it;
 //  * end, arm joints: the absolute joint command RobotEnv.step would receive for this action -- the RelativeActionSpace arithmetic of
 //    env_prologue_team (sim_kernels.h), recomputed READ-ONLY: ORIGIN, LASTA and kHasLastAction are read, never written;
 //  * end, finger slides: where they are (the gripper action is not guarded: the reference's gripper wrapper strips that key before the
@@ -50,33 +51,27 @@ __global__ void __launch_bounds__(64) k_env_guard(GuardArgs G) {
   const int n = G.Q.m;
   const bool live = e < n;
   const size_t ec = live ? e : 0;
-  double qa = 0.0, qb = 0.0;
-  if (live && t < NL) {
-    qa = G.S[(size_t)(L::QPOS + t) * n + ec];
-    qb = qa;
-    if (t < T::NARM) {
-      // RelativeActionSpace.action (python/rcs/envs/base.py:468-488), JOINTS mode: env_prologue_team without its stores
-      double a = G.action[ec * T::NARM + t];
-      if (G.env.relative_to != 0) {
-        const bool last_step = G.env.relative_to == 1;
-        const bool fresh = last_step || !(G.flags[ec] & kHasLastAction);
-        const double origin = last_step ? qa : G.S[(size_t)(L::ORIGIN + t) * n + ec];
-        double lim;
-        if (fresh) {
-          lim = clampd(a, -G.env.max_mov[0], G.env.max_mov[0]);
-        } else {
-          const double la = G.S[(size_t)(L::LASTA + t) * n + ec];
-          lim = clampd(a - la, -G.env.max_mov[0], G.env.max_mov[0]) + la;
-        }
-        a = clampd(origin + lim, G.env.low[t], G.env.high[t]);
+  double qa, fq[7];
+  const bool use_box = query_env_row(G.S, n, e, live, t < NL, L::QPOS, G.box_field, qa, fq);
+  double qb = qa;
+  if (live && t < T::NARM) {
+    // RelativeActionSpace.action (python/rcs/envs/base.py:468-488), JOINTS mode: env_prologue_team without its stores
+    double a = G.action[ec * T::NARM + t];
+    if (G.env.relative_to != 0) {
+      const bool last_step = G.env.relative_to == 1;
+      const bool fresh = last_step || !(G.flags[ec] & kHasLastAction);
+      const double origin = last_step ? qa : G.S[(size_t)(L::ORIGIN + t) * n + ec];
+      double lim;
+      if (fresh) {
+        lim = clampd(a, -G.env.max_mov[0], G.env.max_mov[0]);
+      } else {
+        const double la = G.S[(size_t)(L::LASTA + t) * n + ec];
+        lim = clampd(a - la, -G.env.max_mov[0], G.env.max_mov[0]) + la;
       }
-      qb = a;
+      a = clampd(origin + lim, G.env.low[t], G.env.high[t]);
     }
+    qb = a;
   }
-  const bool use_box = live && G.box_field >= 0;
-  double fq[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) fq[k] = use_box ? G.S[(size_t)(G.box_field + k) * n + ec] : (k == 3 ? 1.0 : 0.0);
   int result = 0;
   double tc = -1.0;
   motion_decide<T, true>(G.Q, lds[team], live, qa, qb, fq, use_box, result, tc);

@@ -899,6 +899,32 @@ void build_collision_tables(const HostModel& h, const DevModel& m, const Collisi
   t.chk.npair = (int)t.chk_ent.size();  // (also the pair table of the contact phase's self-contact stage)
 }
 
+QueryPairs build_query_pairs(const HostModel& h, const CollisionPoints& cp, const std::vector<ContactGeom>& cgeoms,
+                             const std::vector<SelfPair>& chk_pairs, int box_geom, int kinds, bool with_ids) {
+  QueryPairs P;
+  const size_t ng = std::min<size_t>(cgeoms.size(), 32);
+  const bool floor = (kinds & kQueryFloor) && cp.has_plane, box = (kinds & kQueryBox) && box_geom >= 0;
+  for (size_t g = 0; g < ng; ++g) {
+    const ContactGeom& cg = cgeoms[g];
+    if (meshless_hull(cg)) continue;
+    if (floor && cg.plane_ok && cg.link >= 0) P.floor_bits |= 1u << g;
+    // MuJoCo's mask filter against the box geom (contype = conaffinity = 1)
+    if (box && ((h.geom_contype[cg.geom_id] & 1) || (h.geom_conaffinity[cg.geom_id] & 1))) P.box_bits |= 1u << g;
+  }
+  if (!with_ids) return P;
+  for (size_t g = 0; g < ng; ++g)
+    if ((P.floor_bits >> g) & 1u) P.ids.insert(P.ids.end(), {cp.plane_geom, cgeoms[g].geom_id});
+  if (kinds & kQuerySelf)
+    for (const SelfPair& p : chk_pairs) P.ids.insert(P.ids.end(), {cgeoms[p.g0].geom_id, cgeoms[p.g1].geom_id});
+  for (size_t g = 0; g < ng; ++g)
+    if ((P.box_bits >> g) & 1u) {
+      const int gid = cgeoms[g].geom_id;
+      if (cgeoms[g].type == 7) P.ids.insert(P.ids.end(), {box_geom, gid});
+      else P.ids.insert(P.ids.end(), {gid, box_geom});
+    }
+  return P;
+}
+
 bool build_hull_edges(const double* planes, int np, std::vector<HullEdge>& edges, double centre[3]) {
   edges.clear();
   centre[0] = centre[1] = centre[2] = 0;

@@ -95,6 +95,21 @@ void build_collision_tables(const HostModel& h, const DevModel& m, const Collisi
 // the pieces, for the tests: is the pair (a geom welded to the world, a geom of the arm's first link) out of reach in every pose?
 bool never_touch_across_first_hinge(const DevModel& m, const std::vector<double>& cverts, const ContactGeom& a, const ContactGeom& b);
 
+// The pairs the collision and clearance queries cover for `kinds` (kQueryFloor | kQuerySelf | kQueryBox), THE definition: the kernels
+// test floor_bits / box_bits (QueryArgs) and the check's table, rcsh_clearance_pairs reports `ids`, a pair mask is indexed by it.
+// Order: the floor pairs in geom order (geoms the plane admits, on a link, solid: a hull without vertices reports nothing), chk_pairs
+// as the table lists them, the free body's pairs in geom order (solid geoms whose contype / conaffinity meets the box's, 1).  ids are
+// mjModel geom ids in MuJoCo's order within a contact: the free box (a box) before a hull, after a capsule, after a robot box.
+// A group `kinds` leaves out, or whose plane / free body (box_geom < 0) the scene lacks, is empty and its bits are 0.
+struct QueryPairs {
+  std::vector<int32_t> ids;  // [count][2]
+  uint32_t floor_bits = 0, box_bits = 0;  // bit g: table geom g is in the first / the last group
+  int count() const { return (int)ids.size() / 2; }
+};
+// with_ids false: the bits alone (what a launch needs; no list is built).
+QueryPairs build_query_pairs(const HostModel& h, const CollisionPoints& cp, const std::vector<ContactGeom>& cgeoms,
+                             const std::vector<SelfPair>& chk_pairs, int box_geom, int kinds, bool with_ids = true);
+
 // Edges of the convex polytope { x : n_i . x <= d_i } a drawn hull is given as (render.h: the ray caster finds a hull's outline
 // as seen from the camera among them).  Each edge: the two planes that meet in it and its end points.  `centre`: a point
 // inside (the mean of the polytope's vertices).  false: the planes do not bound a polytope this routine can vouch for

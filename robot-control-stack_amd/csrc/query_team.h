@@ -22,12 +22,17 @@
 // this is the check's path-length ("psum") certificate as it stands.  A piece that is not certified is bisected until it is, until
 // a sampled point is in contact (then only the pieces before that point are looked at any more), or until its largest joint
 // travel is at most `resolution`.
+//
+// What the family's other kernels -- the clearance query (clearance_team.h) and the collision guard (guard_team.h) -- take from here:
+// query_config and motion_decide whole (the guard), query_box_frame (the free body's frame: the one quaternion rule) and query_env_row
+// (an environment's own row of the state).  query_row_setup is the row's link frames and world boxes.  Which pairs a query covers is
+// decided once, on the host (model.cpp: build_query_pairs): QueryArgs carries the floor's and the free body's pairs as bits, the self
+// pairs are the check's table.
 #pragma once
 #include "check_team.h"
 
 namespace rcsh {
 
-constexpr int kQueryFloor = 1, kQuerySelf = 2, kQueryBox = 4, kQueryKinds = 7;
 constexpr int kQueryStack = 48;  // pieces a team keeps pending (bisection depth): a piece that would go deeper stays undecided
 // The work per motion row is bounded whatever the resolution: at most kQueryBudget configurations are evaluated by the bisection.  A row
 // that runs out without a contact then samples the grid s = k / kQueryGrid beyond the last piece it settled, in increasing s, and stops
@@ -44,9 +49,10 @@ struct QueryArgs {
   const ContactGeom* geoms;   // the robot's collision geoms (ContactTable::geoms)
   const double* verts;        // their hull vertices
   double plane_n[3], plane_d;
-  int32_t has_plane, plane_geom;   // the floor's mjModel geom id
+  int32_t plane_geom;              // the floor's mjModel geom id
   int32_t box_geom;                // the free body's mjModel geom id (-1: no free body)
-  uint32_t box_ok;                 // bit g: MuJoCo's filters let robot geom g touch the free body
+  uint32_t floor_bits, box_bits;   // bit g: (floor, geom g) / (geom g, free body) is a pair of the query (model.cpp build_query_pairs:
+                                   // the filters, `solid`, the scene and `kinds` all folded in)
   double box_size[3];
   double slide_lo[12], slide_hi[12];  // the interval of each joint the levers hold for (slides: qpos0 -+ the stroke build_self_levers
                                       // charged; hinges: unbounded) -- a segment that leaves it is never certified
@@ -98,24 +104,17 @@ RCSH_D void query_geom_world(const ContactGeom& g, const double* F, double* R, d
   p[0] += L[9]; p[1] += L[10]; p[2] += L[11];
 }
 
-// The collision test of one configuration per team.  Every lane of the wavefront calls it (wave-uniform control flow outside the
-// narrow phase: the team primitives exchange across lanes).  q: the lane's joint (t < NL); fq: the free body's pose (x y z qw qx qy qz,
-// every lane of the team), use_box: test kind 2.  Returns, on every lane of the team, the kinds in contact (bits), and in *pkey the
-// smallest key of a penetrating pair (kind << 16 | index; kQueryNoPair: none).  gaps: lower bounds of the lane's pairs' gaps (0 for a
-// pair in contact, +inf for a pair that is not selected).
+// The row setup of every query kernel: the link frames (world) of the lane's joint value q into S.F, then the geoms' world boxes into
+// S.wbox (lane t: geoms t, t + 16), each behind its fence.  Every lane of the wavefront calls it.
 template <class T>
-RCSH_D uint32_t query_config(const QueryArgs& A, QueryTeamLds<T>& S, double q, bool live, const double* fq, bool use_box, bool want_gaps,
-                             QueryGaps& gp, int* pkey) {
+RCSH_D void query_row_setup(const QueryArgs& A, QueryTeamLds<T>& S, double q) {
   constexpr int NL = T::NL;
   const int t = threadIdx.x & (kTeamLanes - 1);
   const bool valid = t < NL;
-  const int tl = valid ? t : NL - 1;
   const CheckTable& ck = A.ck;
-  const int npair = ck.npair, ngeom = ck.ngeom;
-  // ---- link frames (world)
   {
     KinK kk;
-    kk.load(A.links[tl]);
+    kk.load(A.links[valid ? t : NL - 1]);
     double R[9], p[3];
     link_local_frame(kk, q, R, p);
     scan_frames<T>(R, p);
@@ -128,11 +127,10 @@ RCSH_D uint32_t query_config(const QueryArgs& A, QueryTeamLds<T>& S, double q, b
   }
   stage_fence();
   const double* F = &S.F[0][0];
-  // ---- geoms' world boxes (lane t: geoms t, t + 16)
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int g = t + kTeamLanes * u;
-    if (g < ngeom) {
+    if (g < ck.ngeom) {
       const int link = ck.glink[g];
       double cw[3], Rw[9];
       self_box_world(F, link, ck.geoms[g].c, ck.geoms[g].rot, cw, Rw);
@@ -143,10 +141,13 @@ RCSH_D uint32_t query_config(const QueryArgs& A, QueryTeamLds<T>& S, double q, b
     }
   }
   stage_fence();
-  uint32_t kinds = 0;
-  int key = kQueryNoPair;
-  // the free body's frame
-  double bp[3] = {0, 0, 0}, bR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+}
+
+// the free body's frame from its pose fq (x y z qw qx qy qz); the identity at the origin when it is not tested
+RCSH_D void query_box_frame(const double* fq, bool use_box, double* bp, double* bR) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) bR[k] = k % 4 == 0 ? 1.0 : 0.0;
+  bp[0] = 0.0; bp[1] = 0.0; bp[2] = 0.0;
   if (use_box) {
     // (mju_normalize4: a quaternion of norm below mjMINVAL becomes the identity)
     const double qn = sqrt(fq[3] * fq[3] + fq[4] * fq[4] + fq[5] * fq[5] + fq[6] * fq[6]);
@@ -157,20 +158,52 @@ RCSH_D uint32_t query_config(const QueryArgs& A, QueryTeamLds<T>& S, double q, b
     bR[6] = 2 * (x * z - w * y);     bR[7] = 2 * (y * z + w * x);     bR[8] = 1 - 2 * (x * x + y * y);
     bp[0] = fq[0]; bp[1] = fq[1]; bp[2] = fq[2];
   }
+}
+
+// An environment's own row of the state S ([field][n]): the lane's joint value (0 off the chain) and the free body's pose (box_field
+// < 0: not tested).  Returns use_box.
+RCSH_D bool query_env_row(const double* S, int n, int e, bool live, bool valid, int qpos_field, int box_field, double& q, double* fq) {
+  const size_t ec = live ? e : 0;
+  const int t = threadIdx.x & (kTeamLanes - 1);
+  q = live && valid ? S[(size_t)(qpos_field + t) * n + ec] : 0.0;
+  const bool use_box = live && box_field >= 0;
+#pragma unroll
+  for (int k = 0; k < 7; ++k) fq[k] = use_box ? S[(size_t)(box_field + k) * n + ec] : (k == 3 ? 1.0 : 0.0);
+  return use_box;
+}
+
+// The collision test of one configuration per team.  Every lane of the wavefront calls it (wave-uniform control flow outside the
+// narrow phase: the team primitives exchange across lanes).  q: the lane's joint (t < NL); fq: the free body's pose (x y z qw qx qy qz,
+// every lane of the team), use_box: test kind 2.  Returns, on every lane of the team, the kinds in contact (bits), and in *pkey the
+// smallest key of a penetrating pair (kind << 16 | index; kQueryNoPair: none).  gaps: lower bounds of the lane's pairs' gaps (0 for a
+// pair in contact, +inf for a pair that is not selected).
+template <class T>
+RCSH_D uint32_t query_config(const QueryArgs& A, QueryTeamLds<T>& S, double q, bool live, const double* fq, bool use_box, bool want_gaps,
+                             QueryGaps& gp, int* pkey) {
+  const int t = threadIdx.x & (kTeamLanes - 1);
+  const CheckTable& ck = A.ck;
+  const int npair = ck.npair;
+  query_row_setup<T>(A, S, q);
+  const double* F = &S.F[0][0];
+  uint32_t kinds = 0;
+  int key = kQueryNoPair;
+  double bp[3], bR[9];
+  query_box_frame(fq, use_box, bp, bR);
   const double* bs = A.box_size;
   // ---- kind 0 (floor) and the broad levels of kind 2 (free body): lane t takes geoms t, t + 16
+  const uint32_t fbits = live ? A.floor_bits : 0u, bbits = live && use_box ? A.box_bits : 0u;  // the pairs this call tests
   uint32_t bmask = 0;  // bit u: geom t + 16 u needs the narrow phase against the free body
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     gp.f[u] = INFINITY;
     gp.b[u] = INFINITY;
     const int g = t + kTeamLanes * u;
-    if (!live || g >= ngeom) continue;
+    const bool on_floor = (fbits >> g) & 1u, at_box = (bbits >> g) & 1u;
+    if (!on_floor && !at_box) continue;
     const ContactGeom& cg = A.geoms[g];
-    const bool solid = cg.type != 7 || cg.vert_num > 0;  // (a hull without vertices reports nothing)
     double gR[9], gpos[3];
     query_geom_world(cg, F, gR, gpos);
-    if ((A.kinds & kQueryFloor) && A.has_plane && cg.plane_ok && cg.link >= 0 && solid) {
+    if (on_floor) {
       const double* n = A.plane_n;
       double nl[3];
       mulTv(gR, n, nl);
@@ -193,7 +226,7 @@ RCSH_D uint32_t query_config(const QueryArgs& A, QueryTeamLds<T>& S, double q, b
       }
       gp.f[u] = gap_lb(low);
     }
-    if (use_box && ((A.box_ok >> g) & 1u) && solid) {
+    if (at_box) {
       double hc[3], hh[3], oc[3];
       geom_obb(cg, hc, hh);
       mulmv(gR, hc, oc);

@@ -718,6 +718,24 @@ std::vector<double> tile(const double* row, int width, int n) {
   return v;
 }
 
+// The launch of a team kernel over m rows, four to a wavefront: launch(topo, grid, block) enqueues it for the archetype; `what` names
+// it in the error text.
+template <class F>
+int team_launch(rcsh_sim* s, int32_t m, const char* what, F&& launch) {
+  hipError_t err = hipSuccess;
+  const bool ok = dispatch_topology(s->narm, s->grip, [&](auto topo) {
+    launch(topo, dim3((m + 3) / 4), dim3(64));
+    err = hipGetLastError();
+  });
+  if (!ok) return fail(RCSH_ERR_MODEL, "no kernel instantiated for this archetype");
+  if (err != hipSuccess) return fail(RCSH_ERR_DEVICE, std::string(what) + " launch: " + hipGetErrorString(err));
+  return RCSH_OK;
+}
+// the pair set of a query (model.cpp); the free body's geom is the scene's last, split off its articulated tables
+QueryPairs query_pairs(rcsh_sim* s, int32_t kinds, bool with_ids = true) {
+  return build_query_pairs(s->hm, s->cp, s->cgeoms, s->tables.chk_pairs, s->box.present ? s->hm.ngeom : -1, kinds, with_ids);
+}
+
 // every entry point works on the handle's own GPU, whatever device the calling thread had current
 #define REQUIRE_SIM(s)                                        \
   if (!(s)) return fail(RCSH_ERR_ARG, "null sim handle"); \
@@ -1157,7 +1175,7 @@ int query_finite(const double* a, size_t n, const char* what) {
     if (!std::isfinite(a[i])) return fail(RCSH_ERR_ARG, std::string("non-finite entry in ") + what);
   return RCSH_OK;
 }
-QueryArgs query_args(rcsh_sim* s, int32_t m, int32_t kinds) {
+QueryArgs query_args(rcsh_sim* s, int32_t m, int32_t kinds, const QueryPairs& pairs) {
   const Params P = make_params(s);
   QueryArgs A{};
   A.links = reinterpret_cast<const LinkRec*>(reinterpret_cast<const char*>(s->d_model.get()) + sizeof(DevModel));
@@ -1168,14 +1186,10 @@ QueryArgs query_args(rcsh_sim* s, int32_t m, int32_t kinds) {
   A.verts = s->d_cverts.get();
   for (int k = 0; k < 3; ++k) A.plane_n[k] = s->cp.plane_n[k];
   A.plane_d = s->cp.plane_d;
-  A.has_plane = s->cp.has_plane ? 1 : 0;
   A.plane_geom = s->cp.has_plane ? s->cp.plane_geom : -1;
-  A.box_geom = s->box.present ? s->hm.ngeom : -1;  // (the free body's geom: the scene's last, split off its articulated tables)
-  A.box_ok = 0;
-  for (size_t g = 0; g < s->cgeoms.size() && g < 32; ++g) {
-    const int gid = s->cgeoms[g].geom_id;  // MuJoCo's mask filter against the box geom (contype = conaffinity = 1)
-    if ((s->hm.geom_contype[gid] & 1) || (s->hm.geom_conaffinity[gid] & 1)) A.box_ok |= 1u << g;
-  }
+  A.box_geom = s->box.present ? s->hm.ngeom : -1;
+  A.floor_bits = pairs.floor_bits;
+  A.box_bits = pairs.box_bits;
   for (int k = 0; k < 3; ++k) A.box_size[k] = s->box.size[k];
   for (int L = 0; L < 12; ++L) {
     // (model.cpp build_self_levers: a slide's lever holds over qpos0 -+ its stroke)
@@ -1189,18 +1203,18 @@ QueryArgs query_args(rcsh_sim* s, int32_t m, int32_t kinds) {
   return A;
 }
 int query_launch(rcsh_sim* s, const QueryArgs& A, bool motion) {
-  hipError_t err = hipSuccess;
-  const bool ok = dispatch_topology(s->narm, s->grip, [&](auto topo) {
+  return team_launch(s, A.m, "collision query", [&](auto topo, dim3 grid, dim3 block) {
     using T = decltype(topo);
-    const dim3 grid((A.m + 3) / 4), block(64);
     if (motion) hipLaunchKernelGGL(k_motion_query<T>, grid, block, 0, s->stream, A);
     else hipLaunchKernelGGL(k_collision_query<T>, grid, block, 0, s->stream, A);
-    err = hipGetLastError();
   });
-  if (!ok) return fail(RCSH_ERR_MODEL, "no kernel instantiated for this archetype");
-  if (err != hipSuccess) return fail(RCSH_ERR_DEVICE, std::string("collision query launch: ") + hipGetErrorString(err));
-  return RCSH_OK;
 }
+// Device staging of the host-pointer query forms: slices cut out of d_query in the order they are taken (offsets in bytes, every slice
+// 8-byte aligned; an absent array takes none)
+struct QuerySlices {
+  size_t total = 0;
+  size_t take(size_t bytes) { const size_t at = total; total += align8(bytes); return at; }
+};
 // device pointers in: the answer for a robot without collision geometry is written without a kernel
 int point_query_dev(rcsh_sim* s, const double* q, const double* free_qpos, int32_t m, int32_t kinds, uint8_t* hit, uint8_t* kinds_hit,
                     int32_t* pair) {
@@ -1210,7 +1224,7 @@ int point_query_dev(rcsh_sim* s, const double* q, const double* free_qpos, int32
     if (pair) HIP_TRY(hipMemsetAsync(pair, 0xff, sizeof(int32_t) * 2 * (size_t)m, s->stream));
     return RCSH_OK;
   }
-  QueryArgs A = query_args(s, m, kinds);
+  QueryArgs A = query_args(s, m, kinds, query_pairs(s, kinds, false));
   A.q0 = q; A.free_qpos = free_qpos; A.hit = hit; A.kinds_hit = kinds_hit; A.pair = pair;
   return query_launch(s, A, false);
 }
@@ -1225,9 +1239,14 @@ int motion_query_dev(rcsh_sim* s, const double* q_from, const double* q_to, cons
     HIP_TRY(hipGetLastError());
     return RCSH_OK;
   }
-  QueryArgs A = query_args(s, m, kinds);
+  QueryArgs A = query_args(s, m, kinds, query_pairs(s, kinds, false));
   A.q0 = q_from; A.q1 = q_to; A.free_qpos = free_qpos; A.resolution = resolution; A.result = result; A.t_contact = t_contact;
   return query_launch(s, A, true);
+}
+int motion_check(rcsh_sim* s, int32_t m, int32_t kinds, const double* free_qpos, double resolution) {
+  if (int rc = query_check(s, m, kinds, free_qpos)) return rc;
+  if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(RCSH_ERR_ARG, "resolution must be positive and finite");
+  return RCSH_OK;
 }
 }  // namespace
 
@@ -1241,8 +1260,9 @@ int rcsh_collision_query(rcsh_sim* s, const double* q, const double* free_qpos, 
   const size_t nl = (size_t)s->nl, n = (size_t)m;
   if ((rc = query_finite(q, n * nl, "q"))) return rc;
   if (free_qpos && (rc = query_finite(free_qpos, n * 7, "free_qpos"))) return rc;
-  const size_t oq = 0, of = oq + 8 * n * nl, oh = of + (free_qpos ? 8 * n * 7 : 0), ok = align8(oh + n), op = align8(ok + n), end = op + 8 * n;
-  if ((rc = grow_device(s, s->d_query, end))) return rc;
+  QuerySlices c;
+  const size_t oq = c.take(8 * n * nl), of = c.take(free_qpos ? 8 * n * 7 : 0), oh = c.take(n), ok = c.take(n), op = c.take(8 * n);
+  if ((rc = grow_device(s, s->d_query, c.total))) return rc;
   char* d = static_cast<char*>(s->d_query.p.get());
   HIP_TRY(hipMemcpyAsync(d + oq, q, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
   if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
@@ -1267,16 +1287,16 @@ int rcsh_collision_query_dev(rcsh_sim* s, const double* q_dev, const double* fre
 int rcsh_motion_query(rcsh_sim* s, const double* q_from, const double* q_to, const double* free_qpos, int32_t m, int32_t kinds, double resolution,
                       int32_t* result, double* t_contact) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
-  int rc = query_check(s, m, kinds, free_qpos);
+  int rc = motion_check(s, m, kinds, free_qpos, resolution);
   if (rc) return rc;
-  if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(RCSH_ERR_ARG, "resolution must be positive and finite");
   if (m == 0) return RCSH_OK;
   if (!q_from || !q_to || !result || !t_contact) return fail(RCSH_ERR_ARG, "null argument");
   const size_t nl = (size_t)s->nl, n = (size_t)m;
   if ((rc = query_finite(q_from, n * nl, "q_from")) || (rc = query_finite(q_to, n * nl, "q_to"))) return rc;
   if (free_qpos && (rc = query_finite(free_qpos, n * 7, "free_qpos"))) return rc;
-  const size_t oa = 0, ob = oa + 8 * n * nl, of = ob + 8 * n * nl, orr = of + (free_qpos ? 8 * n * 7 : 0), ot = orr + 8 * n, end = ot + 8 * n;
-  if ((rc = grow_device(s, s->d_query, end))) return rc;
+  QuerySlices c;
+  const size_t oa = c.take(8 * n * nl), ob = c.take(8 * n * nl), of = c.take(free_qpos ? 8 * n * 7 : 0), orr = c.take(4 * n), ot = c.take(8 * n);
+  if ((rc = grow_device(s, s->d_query, c.total))) return rc;
   char* d = static_cast<char*>(s->d_query.p.get());
   HIP_TRY(hipMemcpyAsync(d + oa, q_from, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipMemcpyAsync(d + ob, q_to, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
@@ -1293,9 +1313,8 @@ int rcsh_motion_query(rcsh_sim* s, const double* q_from, const double* q_to, con
 int rcsh_motion_query_dev(rcsh_sim* s, const double* q_from_dev, const double* q_to_dev, const double* free_qpos_dev, int32_t m, int32_t kinds,
                           double resolution, int32_t* result_dev, double* t_contact_dev) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
-  int rc = query_check(s, m, kinds, free_qpos_dev);
+  int rc = motion_check(s, m, kinds, free_qpos_dev, resolution);
   if (rc) return rc;
-  if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(RCSH_ERR_ARG, "resolution must be positive and finite");
   if (m == 0) return RCSH_OK;
   if (!q_from_dev || !q_to_dev || !result_dev || !t_contact_dev) return fail(RCSH_ERR_ARG, "null argument");
   return motion_query_dev(s, q_from_dev, q_to_dev, free_qpos_dev, m, kinds, resolution, result_dev, t_contact_dev);
@@ -1303,35 +1322,6 @@ int rcsh_motion_query_dev(rcsh_sim* s, const double* q_from_dev, const double* q
 
 // ---- clearance queries (csrc/clearance_team.h)
 namespace {
-// The pairs a clearance query covers for `kinds`, in the list's order: the floor pairs in geom order, the check's table, the free
-// body's pairs in geom order -- what query_config tests.  floor_bits / box_bits: the table geoms behind the first and the last group.
-struct ClearList {
-  std::vector<int32_t> ids;  // [count][2] mjModel geom ids, MuJoCo's order within a contact
-  uint32_t floor_bits = 0, box_bits = 0;
-  int count() const { return (int)ids.size() / 2; }
-};
-void clearance_list(rcsh_sim* s, int32_t kinds, ClearList& L) {
-  const int box_geom = s->hm.ngeom;
-  for (size_t g = 0; g < s->cgeoms.size() && g < 32; ++g) {
-    const ContactGeom& cg = s->cgeoms[g];
-    const bool solid = cg.type != 7 || cg.vert_num > 0;
-    if (s->cp.has_plane && cg.plane_ok && cg.link >= 0 && solid) L.floor_bits |= 1u << g;
-    const int gid = cg.geom_id;
-    if (s->box.present && solid && ((s->hm.geom_contype[gid] & 1) || (s->hm.geom_conaffinity[gid] & 1))) L.box_bits |= 1u << g;
-  }
-  if (kinds & kQueryFloor)
-    for (size_t g = 0; g < s->cgeoms.size() && g < 32; ++g)
-      if ((L.floor_bits >> g) & 1u) { L.ids.push_back(s->cp.plane_geom); L.ids.push_back(s->cgeoms[g].geom_id); }
-  if (kinds & kQuerySelf)
-    for (const SelfPair& p : s->tables.chk_pairs) { L.ids.push_back(s->cgeoms[p.g0].geom_id); L.ids.push_back(s->cgeoms[p.g1].geom_id); }
-  if (kinds & kQueryBox)
-    for (size_t g = 0; g < s->cgeoms.size() && g < 32; ++g)
-      if ((L.box_bits >> g) & 1u) {
-        const bool hull = s->cgeoms[g].type == 7;  // (query_pair_ids: the free box before a hull, after a capsule or a robot box)
-        L.ids.push_back(hull ? box_geom : s->cgeoms[g].geom_id);
-        L.ids.push_back(hull ? s->cgeoms[g].geom_id : box_geom);
-      }
-}
 int clearance_check(rcsh_sim* s, int32_t m, int32_t kinds, const double* free_qpos, double d_max) {
   int rc = query_check(s, m, kinds, free_qpos);
   if (rc) return rc;
@@ -1340,66 +1330,42 @@ int clearance_check(rcsh_sim* s, int32_t m, int32_t kinds, const double* free_qp
 }
 struct ClearOut { double* distance; uint8_t* status; int32_t* pair; double* witness; double* grad; };
 // device pointers in; S non-null: the environments' own rows (m = n_envs; box_field as GuardArgs::box_field)
-int clearance_dev(rcsh_sim* s, const double* q, const double* free_qpos, int32_t m, int32_t kinds, const uint8_t* pair_mask, double d_max,
-                  const ClearOut& o, const double* S, int box_field) {
+int clearance_dev(rcsh_sim* s, const QueryPairs& pairs, const double* q, const double* free_qpos, int32_t m, int32_t kinds, const uint8_t* pair_mask,
+                  double d_max, const ClearOut& o, const double* S, int box_field) {
   if (s->cgeoms.empty()) {
     hipLaunchKernelGGL(k_clearance_fill, dim3((m + 63) / 64), dim3(64), 0, s->stream, o.distance, o.status, o.pair, o.witness, o.grad, d_max, m, s->nl);
     HIP_TRY(hipGetLastError());
     return RCSH_OK;
   }
-  ClearList L;
-  clearance_list(s, kinds, L);
   ClearArgs A{};
-  A.Q = query_args(s, m, kinds);
+  A.Q = query_args(s, m, kinds, pairs);
   A.Q.q0 = q; A.Q.free_qpos = free_qpos;
-  A.floor_bits = L.floor_bits; A.box_bits = L.box_bits;
   A.pair_mask = pair_mask; A.d_max = d_max;
   A.distance = o.distance; A.status = o.status; A.pair = o.pair; A.witness = o.witness; A.grad = o.grad;
   A.S = S; A.qpos_field = field_of(s, "qpos"); A.box_field = box_field;
-  hipError_t err = hipSuccess;
-  const bool ok = dispatch_topology(s->narm, s->grip, [&](auto topo) {
-    using T = decltype(topo);
-    hipLaunchKernelGGL(k_clearance_query<T>, dim3((m + 3) / 4), dim3(64), 0, s->stream, A);
-    err = hipGetLastError();
+  return team_launch(s, m, "clearance query", [&](auto topo, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(k_clearance_query<decltype(topo)>, grid, block, 0, s->stream, A);
   });
-  if (!ok) return fail(RCSH_ERR_MODEL, "no kernel instantiated for this archetype");
-  if (err != hipSuccess) return fail(RCSH_ERR_DEVICE, std::string("clearance query launch: ") + hipGetErrorString(err));
-  return RCSH_OK;
-}
-// Device staging of the host-pointer clearance forms, cut out of d_query (offsets in bytes; every slice 8-byte aligned):
-// [q | free_qpos | pair_mask | distance | witness | grad | pair | status]
-struct ClearLayout { size_t q, free_qpos, mask, distance, witness, grad, pair, status, total; };
-ClearLayout clear_layout(size_t n, size_t nl, bool rows, bool free_body, size_t nmask) {
-  ClearLayout c{};
-  c.q = 0;
-  c.free_qpos = c.q + (rows ? 8 * n * nl : 0);
-  c.mask = c.free_qpos + (free_body ? 8 * n * 7 : 0);
-  c.distance = align8(c.mask + nmask);
-  c.witness = c.distance + 8 * n;
-  c.grad = c.witness + 8 * n * 6;
-  c.pair = c.grad + 8 * n * nl;
-  c.status = c.pair + 8 * n;
-  c.total = align8(c.status + n);
-  return c;
 }
 // the host form of both queries: q null: the environments' own rows
 int clearance_host(rcsh_sim* s, const double* q, const double* free_qpos, int32_t m, int32_t kinds, const uint8_t* pair_mask, double d_max,
                    double* distance, uint8_t* status, int32_t* pair, double* witness, double* grad, const double* S, int box_field) {
   const size_t nl = (size_t)s->nl, n = (size_t)m;
-  ClearList L;
-  if (pair_mask) clearance_list(s, kinds, L);
-  const size_t nmask = (size_t)L.count();
-  const ClearLayout c = clear_layout(n, nl, q != nullptr, free_qpos != nullptr, nmask);
+  const QueryPairs pairs = query_pairs(s, kinds, pair_mask != nullptr);
+  const size_t nmask = pair_mask ? (size_t)pairs.count() : 0;
+  QuerySlices c;
+  const size_t oq = c.take(q ? 8 * n * nl : 0), of = c.take(free_qpos ? 8 * n * 7 : 0), om = c.take(nmask);
+  const size_t od = c.take(8 * n), ow = c.take(8 * n * 6), og = c.take(8 * n * nl), op = c.take(8 * n), os = c.take(n);
   int rc = grow_device(s, s->d_query, c.total);
   if (rc) return rc;
   char* d = static_cast<char*>(s->d_query.p.get());
-  if (q) HIP_TRY(hipMemcpyAsync(d + c.q, q, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
-  if (free_qpos) HIP_TRY(hipMemcpyAsync(d + c.free_qpos, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
-  if (nmask) HIP_TRY(hipMemcpyAsync(d + c.mask, pair_mask, nmask, hipMemcpyHostToDevice, s->stream));
-  const ClearOut o{reinterpret_cast<double*>(d + c.distance), reinterpret_cast<uint8_t*>(d + c.status), reinterpret_cast<int32_t*>(d + c.pair),
-                   reinterpret_cast<double*>(d + c.witness), reinterpret_cast<double*>(d + c.grad)};
-  rc = clearance_dev(s, q ? reinterpret_cast<const double*>(d + c.q) : nullptr, free_qpos ? reinterpret_cast<const double*>(d + c.free_qpos) : nullptr,
-                     m, kinds, nmask ? reinterpret_cast<const uint8_t*>(d + c.mask) : nullptr, d_max, o, S, box_field);
+  if (q) HIP_TRY(hipMemcpyAsync(d + oq, q, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
+  if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
+  if (nmask) HIP_TRY(hipMemcpyAsync(d + om, pair_mask, nmask, hipMemcpyHostToDevice, s->stream));
+  const ClearOut o{reinterpret_cast<double*>(d + od), reinterpret_cast<uint8_t*>(d + os), reinterpret_cast<int32_t*>(d + op),
+                   reinterpret_cast<double*>(d + ow), reinterpret_cast<double*>(d + og)};
+  rc = clearance_dev(s, pairs, q ? reinterpret_cast<const double*>(d + oq) : nullptr, free_qpos ? reinterpret_cast<const double*>(d + of) : nullptr,
+                     m, kinds, nmask ? reinterpret_cast<const uint8_t*>(d + om) : nullptr, d_max, o, S, box_field);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(distance, o.distance, 8 * n, hipMemcpyDeviceToHost, s->stream));
   if (status) HIP_TRY(hipMemcpyAsync(status, o.status, n, hipMemcpyDeviceToHost, s->stream));
@@ -1418,8 +1384,7 @@ int rcsh_clearance_pairs(rcsh_sim* s, int32_t kinds, int32_t* geom_ids, int32_t 
   if (!count || capacity < 0 || (capacity > 0 && !geom_ids)) return fail(RCSH_ERR_ARG, "null argument");
   int rc = query_check(s, 0, kinds, nullptr);
   if (rc) return rc;
-  ClearList L;
-  clearance_list(s, kinds, L);
+  const QueryPairs L = query_pairs(s, kinds);
   *count = L.count();
   for (int i = 0; i < L.count() && i < capacity; ++i) { geom_ids[2 * i] = L.ids[2 * i]; geom_ids[2 * i + 1] = L.ids[2 * i + 1]; }
   return RCSH_OK;
@@ -1442,7 +1407,7 @@ int rcsh_clearance_query_dev(rcsh_sim* s, const double* q_dev, const double* fre
   if (rc) return rc;
   if (m == 0) return RCSH_OK;
   if (!q_dev || !distance_dev) return fail(RCSH_ERR_ARG, "null argument");
-  return clearance_dev(s, q_dev, free_qpos_dev, m, kinds, pair_mask_dev, d_max, ClearOut{distance_dev, status_dev, pair_dev, witness_dev, grad_dev},
+  return clearance_dev(s, query_pairs(s, kinds, false), q_dev, free_qpos_dev, m, kinds, pair_mask_dev, d_max, ClearOut{distance_dev, status_dev, pair_dev, witness_dev, grad_dev},
                        nullptr, -1);
 }
 int rcsh_env_clearance(rcsh_sim* s, int32_t kinds, const uint8_t* pair_mask, double d_max, double* distance, uint8_t* status, int32_t* pair,
@@ -1460,7 +1425,7 @@ int rcsh_env_clearance_dev(rcsh_sim* s, int32_t kinds, const uint8_t* pair_mask_
   int rc = clearance_check(s, s->n, kinds, nullptr, d_max);
   if (rc) return rc;
   if (!distance_dev) return fail(RCSH_ERR_ARG, "null argument");
-  return clearance_dev(s, nullptr, nullptr, s->n, kinds, pair_mask_dev, d_max, ClearOut{distance_dev, status_dev, pair_dev, witness_dev, grad_dev},
+  return clearance_dev(s, query_pairs(s, kinds, false), nullptr, nullptr, s->n, kinds, pair_mask_dev, d_max, ClearOut{distance_dev, status_dev, pair_dev, witness_dev, grad_dev},
                        s->S.get(), env_clearance_box_field(s, kinds));
 }
 
@@ -2048,7 +2013,8 @@ int guard_launch(rcsh_sim* s, const double* action_dev, int32_t* result, double*
   }
   GuardArgs G{};
   const bool box = (s->guard.kinds & kQueryBox) && s->box.present;
-  G.Q = query_args(s, s->n, s->guard.kinds & (box ? kQueryKinds : (kQueryFloor | kQuerySelf)));
+  const int32_t kinds = s->guard.kinds & (box ? kQueryKinds : (kQueryFloor | kQuerySelf));
+  G.Q = query_args(s, s->n, kinds, query_pairs(s, kinds, false));
   G.Q.resolution = s->guard.resolution;
   // A finger of the open hand rests ON its joint limit, and the soft limit lets it through by some 10 um (measured: up to 44 um in a
   // rollout): for the motion query such a row has left the stroke the levers were built for and is never certified -- the guard
@@ -2065,15 +2031,9 @@ int guard_launch(rcsh_sim* s, const double* action_dev, int32_t* result, double*
   G.box_field = box ? field_of(s, "box") + kBoxQ : -1;
   G.block_undecided = s->guard.block_undecided ? 1 : 0;
   G.result = result; G.t_contact = t_contact; G.blocked = blocked; G.hold = hold;
-  hipError_t err = hipSuccess;
-  const bool ok = dispatch_topology(s->narm, s->grip, [&](auto topo) {
-    using T = decltype(topo);
-    hipLaunchKernelGGL(k_env_guard<T>, dim3((s->n + 3) / 4), dim3(64), 0, s->stream, G);
-    err = hipGetLastError();
+  return team_launch(s, s->n, "collision guard", [&](auto topo, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(k_env_guard<decltype(topo)>, grid, block, 0, s->stream, G);
   });
-  if (!ok) return fail(RCSH_ERR_MODEL, "no kernel instantiated for this archetype");
-  if (err != hipSuccess) return fail(RCSH_ERR_DEVICE, std::string("collision guard launch: ") + hipGetErrorString(err));
-  return RCSH_OK;
 }
 }  // namespace
 

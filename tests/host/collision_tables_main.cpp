@@ -1,5 +1,5 @@
-// collision_tables_main.cpp -- runs the collision-table builder (csrc/model.cpp: build_collision_tables) on one scene, on the CPU, and
-// prints the tables as JSON (tests/test_collision_tables_cpu.py).  The scene is model.inc, written by tools/export_model_c.py:
+// collision_tables_main.cpp -- runs the collision-table builder (csrc/model.cpp: build_collision_tables) and the queries' pair-set
+// builder (build_query_pairs, for kinds = 1, 2, 4, 7) on one scene, on the CPU, and prints the tables as JSON (tests/test_collision_tables_cpu.py).  The scene is model.inc, written by tools/export_model_c.py:
 //
 //   python tools/export_model_c.py scene.xml > model.inc
 //   g++ -std=c++17 -I. -I<csrc> collision_tables_main.cpp <csrc>/model.cpp -o collision_tables && ./collision_tables
@@ -102,6 +102,16 @@ int main() {
     std::printf("%s[%u, %u, %u, %.9g]", i ? ", " : "", e & 255u, (e >> 8) & 255u, (e >> 16) & 255u, (double)t.chk_ent[i].rsum);
   }
   std::printf("],\n\"chk_unchecked\": %d, \"ctab_npair\": %d, \"chk_npair\": %d, \"chk_ngeom\": %d,\n", t.chk_unchecked, t.ctab.npair, t.chk.npair, t.chk.ngeom);
+  // the queries' pair set (build_query_pairs) per kinds mask, as for a scene whose free body is geom `ngeom` (rcsh_sim_add_free_box: the
+  // scene's last geom, split off the articulated tables)
+  std::printf("\"plane_geom\": %d, \"box_geom\": %d, \"query_pairs\": {", cp.has_plane ? cp.plane_geom : -1, hm.ngeom);
+  for (int kinds : {1, 2, 4, 7}) {
+    const QueryPairs P = build_query_pairs(hm, cp, cgeoms, t.chk_pairs, hm.ngeom, kinds);
+    std::printf("%s\"%d\": {\"floor_bits\": %u, \"box_bits\": %u, \"ids\": [", kinds == 1 ? "" : ", ", kinds, P.floor_bits, P.box_bits);
+    for (int i = 0; i < P.count(); ++i) std::printf("%s[%d, %d]", i ? ", " : "", P.ids[2 * i], P.ids[2 * i + 1]);
+    std::printf("]}");
+  }
+  std::printf("},\n");
   arr("self_lever", t.ctab.self_lever, 12);
   std::vector<double> lev(t.link_lever, t.link_lever + sizeof(t.link_lever) / sizeof(float));
   arr("link_lever", lev.data(), (int)lev.size(), "}\n");

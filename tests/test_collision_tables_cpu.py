@@ -282,3 +282,31 @@ def test_one_box_rule(built, scenes, scene):
         assert (np.abs(local).max(axis=0) >= h - 1e-12).all()  # ... and it is the tightest such box along the geom's axes
         n += 1
     assert n >= 19
+
+
+@pytest.mark.parametrize("scene", SCENES)
+def test_the_queries_pair_set(built, scenes, scene):
+    """The pair set of the collision and clearance queries (csrc/model.cpp: build_query_pairs), held against the filters restated over the
+    scene's arrays.  Floor group: exactly the table geoms the plane admits (contype / conaffinity against the plane geom's), on a link,
+    solid (no hull without vertices), in geom order, the plane first.  Self group: chk_pairs in order.  Free-body group (the program
+    takes the free body to be geom `ngeom`, contype = conaffinity = 1): the solid geoms its mask meets, in geom order, the free box first
+    for a hull and last for a capsule or a box.  The bits name the same geoms, and the three single-kind lists concatenate to kinds = 7."""
+    T, S = built[scene], scenes[scene]
+    A, Q = S.A, T["query_pairs"]
+    plane, box = T["plane_geom"], T["box_geom"]
+    assert plane >= 0 and box == int(S.cm.ngeom)
+    table = T["geoms"]
+    solid = lambda g: g["type"] != 7 or g["vert_num"] > 0  # noqa: E731
+    admits = lambda a, b: bool((A["geom_contype"][a] & A["geom_conaffinity"][b]) or (A["geom_contype"][b] & A["geom_conaffinity"][a]))  # noqa: E731
+    floor = [i for i, g in enumerate(table) if admits(plane, g["geom_id"]) and S.link_of_body(int(A["geom_bodyid"][g["geom_id"]])) >= 0 and solid(g)]
+    free = [i for i, g in enumerate(table) if ((A["geom_contype"][g["geom_id"]] & 1) or (A["geom_conaffinity"][g["geom_id"]] & 1)) and solid(g)]
+    assert len(floor) > 0 and len(free) > 0
+    bits = lambda idx: sum(1 << i for i in idx)  # noqa: E731
+    assert Q["1"]["ids"] == [[plane, table[i]["geom_id"]] for i in floor]
+    assert (Q["1"]["floor_bits"], Q["1"]["box_bits"]) == (bits(floor), 0)
+    assert Q["2"]["ids"] == [[table[p[0]]["geom_id"], table[p[1]]["geom_id"]] for p in T["chk_pairs"]] and len(Q["2"]["ids"]) > 0
+    assert (Q["2"]["floor_bits"], Q["2"]["box_bits"]) == (0, 0)
+    assert Q["4"]["ids"] == [[box, table[i]["geom_id"]] if table[i]["type"] == 7 else [table[i]["geom_id"], box] for i in free]
+    assert (Q["4"]["floor_bits"], Q["4"]["box_bits"]) == (0, bits(free))
+    assert Q["7"]["ids"] == Q["1"]["ids"] + Q["2"]["ids"] + Q["4"]["ids"]
+    assert (Q["7"]["floor_bits"], Q["7"]["box_bits"]) == (bits(floor), bits(free))

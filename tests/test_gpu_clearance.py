@@ -224,6 +224,11 @@ def test_pair_list(name):
             seen += 1
             assert frozenset(k) in lset, k
     assert seen > 0
+    # ... and so is every pair the point query reports for a row it finds in contact: one pair set behind both queries
+    hit, _, pair = robot.check_collision(q, free_qpos=boxes, kinds=7)
+    assert hit.any()
+    for r in np.flatnonzero(hit):
+        assert (int(pair[r, 0]), int(pair[r, 1])) in listed, (r, pair[r])
     if name.startswith("fr3"):
         # the base link's hull against link 1's (0.994 mm apart in every pose) is a pair the tables drop
         base = {g for g in range(sc.ngeom) if sc.weld[sc.gbody[g]] == 0 and sc.gtype[g] != CC.PLANE}
