@@ -302,6 +302,57 @@ int rcsh_env_clearance(rcsh_sim* sim, int32_t kinds, const uint8_t* pair_mask, d
 int rcsh_env_clearance_dev(rcsh_sim* sim, int32_t kinds, const uint8_t* pair_mask_dev, double d_max, double* distance_dev,
                            uint8_t* status_dev, int32_t* pair_dev, double* witness_dev, double* grad_dev);
 
+/* ---- dynamics queries: the joint-space inertia, the bias forces and the TCP Jacobian at caller-supplied states
+ * (csrc/dynamics_team.h).  What a model-based controller reads off the reference's `sim.data` -- qM (mj_fullM), qfrc_bias,
+ * qfrc_gravcomp, mj_jac of the TCP -- and what the reference's hardware driver takes from libfranka every cycle (model.mass, coriolis,
+ * gravity, zeroJacobian; extensions/rcs_fr3/src/hw/FR3.cpp:241-340), for M rows at once.  Like the collision queries
+ * rcsh_dynamics_query reads and writes NO per-environment state, is independent of n_envs and runs on the handle's stream.
+ * Rows are [M][nl], the robot chain's joints including the finger slides (rad, m): q; qvel (rad/s, m/s; NULL: zero); qacc_in
+ * (rad/s^2, m/s^2; read only when qfrc_inverse is asked for); qfrc_in (N m, N; read only when qacc is asked for).  In a scene with a
+ * free body the query covers the chain's nl degrees of freedom: the body's block of the inertia is decoupled from them.
+ * Every output pointer of rcsh_dynamics_out may be NULL (not wanted); an output's bits do not depend on which others are asked for.
+ * Per row, SI units, MuJoCo's signs:
+ *   qM [M][nl][nl]       the full symmetric joint-space inertia, armature on the diagonal (mj_fullM of mjData.qM);
+ *   qfrc_bias [M][nl]    Coriolis, centrifugal and gravity forces C(q, qvel) qvel + g(q): inverse dynamics at zero acceleration
+ *                        (mjData.qfrc_bias; the equation of motion is M qacc + qfrc_bias = applied forces);
+ *   gravity [M][nl]      qfrc_bias at qvel = 0, i.e. g(q); the Coriolis / centrifugal part is qfrc_bias - gravity;
+ *   qfrc_gravcomp [M][nl] the gravity-compensation force of the bodies' `gravcomp` (mjData.qfrc_gravcomp: a passive or, with
+ *                        actuatorgravcomp, an actuator-side force that the stepping kernels ADD to the applied forces; it equals
+ *                        `gravity` where every body has gravcomp = 1);
+ *   jac [M][6][nl]       the geometric Jacobian of the TCP: rows 0-2 d(position)/dq_j, rows 3-5 the angular velocity per unit joint
+ *                        rate, expressed in the robot-base frame -- the frame rcsh_ik_forward reports its pose in, so central
+ *                        differences of rcsh_ik_forward reproduce it.  The TCP is the pose rcsh_ik_forward returns for the same
+ *                        tcp_offset7 (x y z qx qy qz qw): the attachment site composed with the INVERSE offset (reference quirk Q7);
+ *                        tcp_offset7 NULL: the site itself (not the robot config's offset).  Columns of joints that are not
+ *                        ancestors of the site's link (the finger slides) are zero;
+ *   qfrc_inverse [M][nl] M qacc_in + qfrc_bias: rigid-body inverse dynamics of the chain;
+ *   qacc [M][nl]         M^-1 (qfrc_in - qfrc_bias) by the LDL^T factorisation the stepping kernels use: forward dynamics of the
+ *                        UNCONSTRAINED chain.
+ * NOT included in any output: actuator forces, joint damping, dry friction (frictionloss), joint-limit, equality (the fingers'
+ * coupling) and contact forces; the caller adds what it models to qfrc_in.
+ * RCSH_ERR_STATE: no robot attached.  RCSH_ERR_ARG: M < 0; a null q or a null `out` where M > 0; qfrc_inverse asked for without
+ * qacc_in, or qacc without qfrc_in; a non-finite input entry (host forms only: the _dev forms do not read the values on the host); a
+ * tcp_offset7 quaternion of zero norm.  M = 0 does nothing.  tcp_offset7 is a host pointer in both forms.
+ * rcsh_env_dynamics asks the same once per environment (M = n_envs): the row is the environment's own chain qpos and qvel; qacc_in
+ * and qfrc_in are [N][nl] as above.  It writes nothing but its outputs. */
+typedef struct rcsh_dynamics_out {
+  double* qM;             /* [M][nl][nl] */
+  double* qfrc_bias;      /* [M][nl] */
+  double* gravity;        /* [M][nl] */
+  double* qfrc_gravcomp;  /* [M][nl] */
+  double* jac;            /* [M][6][nl] */
+  double* qfrc_inverse;   /* [M][nl]; needs qacc_in */
+  double* qacc;           /* [M][nl]; needs qfrc_in */
+} rcsh_dynamics_out;
+int rcsh_dynamics_query(rcsh_sim* sim, const double* q, const double* qvel, const double* qacc_in, const double* qfrc_in, int32_t m,
+                        const double* tcp_offset7, const rcsh_dynamics_out* out);
+int rcsh_dynamics_query_dev(rcsh_sim* sim, const double* q_dev, const double* qvel_dev, const double* qacc_in_dev,
+                            const double* qfrc_in_dev, int32_t m, const double* tcp_offset7, const rcsh_dynamics_out* out_dev);
+int rcsh_env_dynamics(rcsh_sim* sim, const double* qacc_in, const double* qfrc_in, const double* tcp_offset7,
+                      const rcsh_dynamics_out* out);
+int rcsh_env_dynamics_dev(rcsh_sim* sim, const double* qacc_in_dev, const double* qfrc_in_dev, const double* tcp_offset7,
+                          const rcsh_dynamics_out* out_dev);
+
 /* SimGripper(sim, cfg) -- rcs.cpp:508-515, SimGripper.cpp:13-39 */
 int rcsh_sim_add_gripper(rcsh_sim* sim, const rcsh_gripper_desc* gripper);
 /* Gripper.set_normalized_width -- rcs.cpp:383-384, SimGripper.cpp:79-92 (RCSH_ERR_ARG outside [0,1] / force<0) */

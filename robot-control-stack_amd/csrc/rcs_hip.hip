@@ -21,6 +21,7 @@
 #include "render.h"
 #include "query_team.h"
 #include "clearance_team.h"
+#include "dynamics_team.h"
 #include "guard_team.h"
 #include "episode_team.h"
 
@@ -1427,6 +1428,117 @@ int rcsh_env_clearance_dev(rcsh_sim* s, int32_t kinds, const uint8_t* pair_mask_
   if (!distance_dev) return fail(RCSH_ERR_ARG, "null argument");
   return clearance_dev(s, query_pairs(s, kinds, false), nullptr, nullptr, s->n, kinds, pair_mask_dev, d_max, ClearOut{distance_dev, status_dev, pair_dev, witness_dev, grad_dev},
                        s->S.get(), env_clearance_box_field(s, kinds));
+}
+
+// ---- dynamics queries (csrc/dynamics_team.h)
+namespace {
+// what both forms check before anything is read; fills the TCP point in the site link's frame
+int dynamics_check(rcsh_sim* s, int32_t m, const double* qacc_in, const double* qfrc_in, const double* tcp7, const rcsh_dynamics_out* out,
+                   double* tcp_p) {
+  if (m < 0) return fail(RCSH_ERR_ARG, "negative query count");
+  if (m > 0 && !out) return fail(RCSH_ERR_ARG, "null argument");
+  if (out && out->qfrc_inverse && !qacc_in) return fail(RCSH_ERR_ARG, "qfrc_inverse asked for without qacc_in");
+  if (out && out->qacc && !qfrc_in) return fail(RCSH_ERR_ARG, "qacc asked for without qfrc_in");
+  // the pose rcsh_ik_forward reports is site * offset^-1 (quirk Q7): its origin in the site's frame is -R_offset^T t_offset
+  double off[3] = {0.0, 0.0, 0.0};
+  if (tcp7) {
+    if (int rc = query_finite(tcp7, 7, "tcp_offset7")) return rc;
+    const double n = std::sqrt(tcp7[3] * tcp7[3] + tcp7[4] * tcp7[4] + tcp7[5] * tcp7[5] + tcp7[6] * tcp7[6]);
+    if (!(n > 0.0)) return fail(RCSH_ERR_ARG, "tcp_offset7 quaternion of zero norm");
+    const double qn[4] = {tcp7[3] / n, tcp7[4] / n, tcp7[5] / n, tcp7[6] / n};
+    double Rt[9];
+    quat_to_mat(qn, Rt);
+    for (int k = 0; k < 3; ++k) off[k] = -(Rt[k] * tcp7[0] + Rt[3 + k] * tcp7[1] + Rt[6 + k] * tcp7[2]);
+  }
+  for (int r = 0; r < 3; ++r)
+    tcp_p[r] = s->dm.site_pos[r] + s->dm.site_rot[3 * r] * off[0] + s->dm.site_rot[3 * r + 1] * off[1] + s->dm.site_rot[3 * r + 2] * off[2];
+  return RCSH_OK;
+}
+// device pointers in; S non-null: the environments' own rows (m = n_envs)
+int dynamics_dev(rcsh_sim* s, const double* q, const double* qvel, const double* qacc_in, const double* qfrc_in, int32_t m, const double* tcp_p,
+                 const rcsh_dynamics_out& o, const double* S) {
+  DynArgs A{};
+  A.links = reinterpret_cast<const LinkRec*>(reinterpret_cast<const char*>(s->d_model.get()) + sizeof(DevModel));
+  A.m = m;
+  A.site_link = s->dm.site_link;
+  for (int k = 0; k < 3; ++k) { A.gravity[k] = s->dm.gravity[k]; A.tcp_p[k] = tcp_p[k]; }
+  const double bq[4] = {s->dm.base_quat[1], s->dm.base_quat[2], s->dm.base_quat[3], s->dm.base_quat[0]};
+  quat_to_mat(bq, A.base_R);
+  A.q = q; A.qvel = qvel; A.qacc_in = qacc_in; A.qfrc_in = qfrc_in;
+  A.o = DynOut{o.qM, o.qfrc_bias, o.gravity, o.qfrc_gravcomp, o.jac, o.qfrc_inverse, o.qacc};
+  A.S = S; A.qpos_field = field_of(s, "qpos"); A.qvel_field = field_of(s, "qvel");
+  return team_launch(s, m, "dynamics query", [&](auto topo, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(k_dynamics_query<decltype(topo)>, grid, block, 0, s->stream, A);
+  });
+}
+// the host form of both queries: q null: the environments' own rows
+int dynamics_host(rcsh_sim* s, const double* q, const double* qvel, const double* qacc_in, const double* qfrc_in, int32_t m, const double* tcp_p,
+                  const rcsh_dynamics_out& o, const double* S) {
+  const size_t nl = (size_t)s->nl, n = (size_t)m, row = 8 * n * nl;
+  const double* in[4] = {q, qvel, o.qfrc_inverse ? qacc_in : nullptr, o.qacc ? qfrc_in : nullptr};
+  const char* names[4] = {"q", "qvel", "qacc_in", "qfrc_in"};
+  for (int k = 0; k < 4; ++k)
+    if (in[k])
+      if (int rc = query_finite(in[k], n * nl, names[k])) return rc;
+  double* const host[7] = {o.qM, o.qfrc_bias, o.gravity, o.qfrc_gravcomp, o.jac, o.qfrc_inverse, o.qacc};
+  const size_t bytes[7] = {row * nl, row, row, row, row * 6, row, row};
+  QuerySlices c;
+  size_t oi[4], oo[7];
+  for (int k = 0; k < 4; ++k) oi[k] = c.take(in[k] ? row : 0);
+  for (int k = 0; k < 7; ++k) oo[k] = c.take(host[k] ? bytes[k] : 0);
+  int rc = grow_device(s, s->d_query, c.total);
+  if (rc) return rc;
+  char* d = static_cast<char*>(s->d_query.p.get());
+  const double* din[4];
+  for (int k = 0; k < 4; ++k) {
+    din[k] = in[k] ? reinterpret_cast<const double*>(d + oi[k]) : nullptr;
+    if (in[k]) HIP_TRY(hipMemcpyAsync(d + oi[k], in[k], row, hipMemcpyHostToDevice, s->stream));
+  }
+  double* dout[7];
+  for (int k = 0; k < 7; ++k) dout[k] = host[k] ? reinterpret_cast<double*>(d + oo[k]) : nullptr;
+  const rcsh_dynamics_out od{dout[0], dout[1], dout[2], dout[3], dout[4], dout[5], dout[6]};
+  if ((rc = dynamics_dev(s, din[0], din[1], din[2], din[3], m, tcp_p, od, S))) return rc;
+  for (int k = 0; k < 7; ++k)
+    if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], dout[k], bytes[k], hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RCSH_OK;
+}
+}  // namespace
+
+int rcsh_dynamics_query(rcsh_sim* s, const double* q, const double* qvel, const double* qacc_in, const double* qfrc_in, int32_t m,
+                        const double* tcp_offset7, const rcsh_dynamics_out* out) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  double tcp_p[3];
+  int rc = dynamics_check(s, m, qacc_in, qfrc_in, tcp_offset7, out, tcp_p);
+  if (rc) return rc;
+  if (m == 0) return RCSH_OK;
+  if (!q) return fail(RCSH_ERR_ARG, "null argument");
+  return dynamics_host(s, q, qvel, qacc_in, qfrc_in, m, tcp_p, *out, nullptr);
+}
+int rcsh_dynamics_query_dev(rcsh_sim* s, const double* q_dev, const double* qvel_dev, const double* qacc_in_dev, const double* qfrc_in_dev,
+                            int32_t m, const double* tcp_offset7, const rcsh_dynamics_out* out_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  double tcp_p[3];
+  int rc = dynamics_check(s, m, qacc_in_dev, qfrc_in_dev, tcp_offset7, out_dev, tcp_p);
+  if (rc) return rc;
+  if (m == 0) return RCSH_OK;
+  if (!q_dev) return fail(RCSH_ERR_ARG, "null argument");
+  return dynamics_dev(s, q_dev, qvel_dev, qacc_in_dev, qfrc_in_dev, m, tcp_p, *out_dev, nullptr);
+}
+int rcsh_env_dynamics(rcsh_sim* s, const double* qacc_in, const double* qfrc_in, const double* tcp_offset7, const rcsh_dynamics_out* out) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  double tcp_p[3];
+  int rc = dynamics_check(s, s->n, qacc_in, qfrc_in, tcp_offset7, out, tcp_p);
+  if (rc) return rc;
+  return dynamics_host(s, nullptr, nullptr, qacc_in, qfrc_in, s->n, tcp_p, *out, s->S.get());
+}
+int rcsh_env_dynamics_dev(rcsh_sim* s, const double* qacc_in_dev, const double* qfrc_in_dev, const double* tcp_offset7,
+                          const rcsh_dynamics_out* out_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  double tcp_p[3];
+  int rc = dynamics_check(s, s->n, qacc_in_dev, qfrc_in_dev, tcp_offset7, out_dev, tcp_p);
+  if (rc) return rc;
+  return dynamics_dev(s, nullptr, nullptr, qacc_in_dev, qfrc_in_dev, s->n, tcp_p, *out_dev, s->S.get());
 }
 
 int rcsh_robot_get_state(rcsh_sim* s, uint8_t* ik_success, uint8_t* collision, uint8_t* is_moving, uint8_t* is_arrived,

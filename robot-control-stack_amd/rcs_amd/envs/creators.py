@@ -192,6 +192,20 @@ class VecSimEnv:
         _lib.check(self._L.rcsh_env_clearance_dev(self.sim._h, kinds, p(pair_mask_dev), float(d_max), p(distance_dev), p(status_dev),
                                                   p(pair_dev), p(witness_dev), p(grad_dev)))
 
+    # ---- dynamics (csrc/dynamics_team.h): on demand, not part of step
+    def dynamics(self, want=None, qacc=None, qfrc=None, tcp_offset=None) -> dict:
+        """Every environment's joint-space inertia, bias forces and TCP Jacobian where it is now: its own chain ``qpos`` and ``qvel``.
+        ``want``, ``qacc`` / ``qfrc`` ([N, nl], for ``qfrc_inverse`` / ``qacc``), ``tcp_offset`` and the returned dict of arrays as
+        :meth:`rcs_amd.sim.SimRobot.dynamics_query`.  Reads the state, writes none of it."""
+        n, nl = self.n_envs, int(self.sim.model.nq)
+        want = self.robot._dynamics_want(want, qacc, qfrc)
+        rows = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (n, nl)))  # noqa: E731
+        a, f = rows(qacc), rows(qfrc)
+        arrays, out = self.robot._dynamics_buffers(want, n, nl)
+        tcp = sim.DeviceKinematics._tcp(tcp_offset)
+        _lib.check(self._L.rcsh_env_dynamics(self.sim._h, _lib.ptr(a), _lib.ptr(f), _lib.ptr(tcp), C.byref(out)))
+        return arrays
+
     def _guard_info(self, i: dict[str, Any]):
         """info["guard_*"] of a guarded step; returns ``blocked`` where it truncates (else None)."""
         if not self.guard_enabled:

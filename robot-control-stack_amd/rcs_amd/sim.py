@@ -357,7 +357,8 @@ class DeviceKinematics:
     def __init__(self, sim: "Sim", dof: int):
         self.sim, self.dof = sim, dof
 
-    def _tcp(self, tcp_offset):
+    @staticmethod
+    def _tcp(tcp_offset):
         if tcp_offset is None:
             return None
         v = tcp_offset.as_vec7() if isinstance(tcp_offset, common.Pose) else np.asarray(tcp_offset, dtype=np.float64)
@@ -383,6 +384,21 @@ class DeviceKinematics:
         out = np.zeros((n, 7))
         _lib.check(self.sim._L.rcsh_ik_forward(self.sim._h, _lib.ptr(q0), _lib.ptr(self._tcp(tcp_offset)), _lib.ptr(out)))
         return out
+
+    def jacobian(self, q0, tcp_offset=None) -> np.ndarray:
+        """q0 [M, dof] or [M, nq] (any M; the finger slides do not move the TCP) -> [M, 6, nq]: the geometric Jacobian of the pose
+        ``forward`` returns -- rows 0-2 d(position)/dq, rows 3-5 angular velocity per unit joint rate, robot-base frame; finger
+        columns zero.  ``tcp_offset`` None: the attachment site itself (include/rcs_hip.h, rcsh_dynamics_query)."""
+        nq = int(self.sim.model.nq)
+        q0 = np.atleast_2d(np.asarray(q0, dtype=np.float64))
+        rows = np.zeros((q0.shape[0], nq))
+        w = nq if q0.shape[1] >= nq else self.dof
+        rows[:, :w] = q0[:, :w]
+        jac = np.zeros((rows.shape[0], 6, nq))
+        out = _lib.DynamicsOut(jac=jac.ctypes.data)
+        _lib.check(self.sim._L.rcsh_dynamics_query(self.sim._h, _lib.ptr(rows), None, None, None, rows.shape[0], _lib.ptr(self._tcp(tcp_offset)),
+                                                   C.byref(out)))
+        return jac
 
 
 class SimRobot:
@@ -622,6 +638,45 @@ class SimRobot:
         _lib.check(self._L.rcsh_clearance_query(self.sim._h, _lib.ptr(rows), _lib.ptr(fq), m, int(kinds), _lib.ptr(mask), float(d_max),
                                                 _lib.ptr(dist), _lib.ptr(status), _lib.ptr(pair), _lib.ptr(wit), _lib.ptr(grad)))
         return dist, status, pair, wit, grad
+
+    # outputs of the dynamics queries, in the order of rcsh_dynamics_out, with the shape of one row
+    DYNAMICS_OUTPUTS = ("qM", "qfrc_bias", "gravity", "qfrc_gravcomp", "jac", "qfrc_inverse", "qacc")
+
+    def _dynamics_want(self, want, qacc, qfrc) -> tuple:
+        if want is None:
+            want = tuple(k for k in self.DYNAMICS_OUTPUTS if (k != "qfrc_inverse" or qacc is not None) and (k != "qacc" or qfrc is not None))
+        want = (want,) if isinstance(want, str) else tuple(want)
+        unknown = [k for k in want if k not in self.DYNAMICS_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown dynamics output {unknown}: one of {self.DYNAMICS_OUTPUTS}")
+        return want
+
+    def _dynamics_buffers(self, want, m: int, nl: int):
+        shape = {"qM": (m, nl, nl), "jac": (m, 6, nl)}
+        arrays = {k: np.zeros(shape.get(k, (m, nl))) for k in want}
+        return arrays, _lib.DynamicsOut(**{k: a.ctypes.data for k, a in arrays.items()})
+
+    def dynamics_query(self, q, qvel=None, qacc=None, qfrc=None, tcp_offset=None, want=None, finger_qpos=None) -> dict:
+        """What a model-based controller reads off ``sim.data`` (``qM``, ``qfrc_bias``, ``qfrc_gravcomp``, ``mj_jac``), for M
+        caller-supplied states at once, without touching any environment's state.
+
+        q: rows as ``check_collision``; qvel / qacc / qfrc: [M, nl] (qvel None: zero).  ``want``: names out of
+        ``DYNAMICS_OUTPUTS`` (None: every output its inputs allow).  Returns a dict of arrays: ``qM`` [M, nl, nl] (full, symmetric,
+        armature included), ``qfrc_bias`` [M, nl] (Coriolis + centrifugal + gravity), ``gravity`` [M, nl] (qfrc_bias at qvel = 0;
+        Coriolis is the difference), ``qfrc_gravcomp`` [M, nl], ``jac`` [M, 6, nl] (the TCP's geometric Jacobian in the robot-base
+        frame, the frame of ``get_ik().forward``; ``tcp_offset`` None: the attachment site), ``qfrc_inverse`` [M, nl] = M qacc +
+        qfrc_bias (needs ``qacc``), ``qacc`` [M, nl] = M^-1 (qfrc - qfrc_bias) (needs ``qfrc``).  No actuator, damping, friction,
+        limit, equality or contact force enters any of them (include/rcs_hip.h, rcsh_dynamics_query)."""
+        rows = self._query_rows(q, finger_qpos, "q")
+        m, nl = rows.shape
+        want = self._dynamics_want(want, qacc, qfrc)
+
+        like = lambda x: None if x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (m, nl)))  # noqa: E731
+        v, a, f = like(qvel), like(qacc), like(qfrc)
+        arrays, out = self._dynamics_buffers(want, m, nl)
+        tcp = DeviceKinematics._tcp(tcp_offset)
+        _lib.check(self._L.rcsh_dynamics_query(self.sim._h, _lib.ptr(rows), _lib.ptr(v), _lib.ptr(a), _lib.ptr(f), m, _lib.ptr(tcp), C.byref(out)))
+        return arrays
 
 
 @dataclass
