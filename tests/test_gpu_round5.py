@@ -32,6 +32,8 @@ def test_headline_rollout_matches_the_resolving_oracle_for_1000_steps():
     from parity_util import run_headline_resolved_parity
 
     rep = run_headline_resolved_parity(n_envs=64, n_steps=1000, seed=0)
+    # (contacts that began and ended inside one launch: what this rollout happens to hold of what tests/test_gpu_certificate_cases.py makes on purpose)
+    print(f"\ngraze steps: {int(rep['graze_steps'].sum())} in {int((rep['graze_steps'] > 0).sum())} environments")
     touched = rep["first_contact"] >= 0
     assert touched.sum() >= 8, rep  # (some environments do reach the floor / themselves)
     assert rep["overflow_envs"].sum() == 0 and not rep["unresolved"].any(), rep
