@@ -302,6 +302,63 @@ int rcsh_env_clearance(rcsh_sim* sim, int32_t kinds, const uint8_t* pair_mask, d
 int rcsh_env_clearance_dev(rcsh_sim* sim, int32_t kinds, const uint8_t* pair_mask_dev, double d_max, double* distance_dev,
                            uint8_t* status_dev, int32_t* pair_dev, double* witness_dev, double* grad_dev);
 
+/* ---- swept clearance: the smallest distance along a joint-space motion, bracketed (csrc/swept_team.h).
+ * A row is the straight segment q(s) = q_from + s (q_to - q_from), s in [0, 1], over the nl chain joints (finger slides included), as
+ * rcsh_motion_query takes it.  kinds, free_qpos (the body stands still at that pose for the whole segment), pair_mask (indexed by
+ * rcsh_clearance_pairs) and d_max mean what they mean for rcsh_clearance_query; `tolerance` (> 0, m) is the bracket width asked for;
+ * `resolution` (> 0, rad or m) is rcsh_motion_query's: a piece whose largest joint travel is at most this is not split further.
+ * The bracket rests on the motion certificate's levers: over a piece of width w in s a pair's distance changes by at most w L_p, so
+ *   min over [a, b] of d_p >= (d_p(a) + d_p(b) - w L_p) / 2.
+ * `distance` is the smallest exact clearance among the sampled configurations (an upper bound of the minimum, attained at `s`);
+ * `lower` is the smallest bound of any piece of the segment (a PROVEN lower bound of the clearance over the whole segment).
+ * Every output pointer of rcsh_swept_out but `distance` may be NULL.  Per row:
+ *   distance [M]   the clearance at q(s): what rcsh_clearance_query answers for that configuration;
+ *   lower [M]      lower <= distance; never more than the true minimum where it is finite;
+ *   s [M]          the parameter at which `distance` is attained;
+ *   pair [M][2], witness [M][6], grad [M][nl]   rcsh_clearance_query's outputs at q(s): the same conventions, tie rule and capsule-core
+ *                  witnesses;
+ *   evals [M]      configurations evaluated for the row: at most 2048 while it minimises, at most 256 more once a contact was sampled;
+ *   status [M]     0 bracketed: distance - lower <= tolerance;
+ *                  1 beyond: proven -- no selected pair comes within d_max anywhere on the segment: distance == lower == d_max, s = -1,
+ *                    pair -1 -1, witness and grad zeros;
+ *                  2 contact: a sampled configuration penetrates by more than 1e-9 m (the point query's predicate).  s is the smallest
+ *                    sampled parameter in contact, after the part of the segment before it has been searched as rcsh_motion_query
+ *                    searches it (pieces certified free, or bisected down to `resolution`); distance, pair, witness and grad are
+ *                    rcsh_clearance_query's status-2 answer there; lower = -inf.  The minimisation stops: the deepest penetration along
+ *                    the path is not looked for;
+ *                  3 open: the bracket is valid but wider than `tolerance` -- the evaluation budget or the piece stack ran out,
+ *                    `resolution` stopped the splitting, the distance iteration of the best sample met its cap, or a finger slide
+ *                    leaves the stroke the levers were built for (then nothing can be proven: lower = -inf, and the segment is sampled
+ *                    at s = k / 32).  Where no sampled configuration came within d_max but that could not be proven for the whole
+ *                    segment, distance == d_max, s = -1, pair -1 -1 and lower < d_max.
+ * For every status but 1, `distance` is a value the clearance really takes on the segment, at `s`; a q_from == q_to row gives s = 0
+ * and the point query's answer.  Results depend on the row alone.  The bound is Lipschitz only: a distance that stays flat while the
+ * levers are large (joint 1 turning the arm about the vertical above the floor) converges slowly and ends as status 3 with a valid
+ * bracket.  One mask per call; no per-pair output.
+ * RCSH_ERR_MODEL and RCSH_ERR_ARG as rcsh_clearance_query, plus tolerance or resolution that is not finite or is <= 0.  M = 0 does
+ * nothing; an error leaves outputs and state untouched.  Robots without collision geometry answer status 1 for every row.
+ * rcsh_env_swept_clearance asks the same once per environment (M = n_envs): the start is the environment's own chain configuration,
+ * the end is q_to [N][nl], the free body is at the environment's own pose.  It writes nothing but its outputs. */
+typedef struct rcsh_swept_out {
+  double* distance;  /* [M] (required) */
+  double* lower;     /* [M] */
+  double* s;         /* [M] */
+  int32_t* pair;     /* [M][2] */
+  double* witness;   /* [M][6] */
+  double* grad;      /* [M][nl] */
+  int32_t* evals;    /* [M] */
+  uint8_t* status;   /* [M] */
+} rcsh_swept_out;
+int rcsh_swept_clearance(rcsh_sim* sim, const double* q_from, const double* q_to, const double* free_qpos, int32_t m, int32_t kinds,
+                         const uint8_t* pair_mask, double d_max, double tolerance, double resolution, const rcsh_swept_out* out);
+int rcsh_swept_clearance_dev(rcsh_sim* sim, const double* q_from_dev, const double* q_to_dev, const double* free_qpos_dev, int32_t m,
+                             int32_t kinds, const uint8_t* pair_mask_dev, double d_max, double tolerance, double resolution,
+                             const rcsh_swept_out* out_dev);
+int rcsh_env_swept_clearance(rcsh_sim* sim, const double* q_to, int32_t kinds, const uint8_t* pair_mask, double d_max, double tolerance,
+                             double resolution, const rcsh_swept_out* out);
+int rcsh_env_swept_clearance_dev(rcsh_sim* sim, const double* q_to_dev, int32_t kinds, const uint8_t* pair_mask_dev, double d_max,
+                                 double tolerance, double resolution, const rcsh_swept_out* out_dev);
+
 /* ---- dynamics queries: the joint-space inertia, the bias forces and the TCP Jacobian at caller-supplied states
  * (csrc/dynamics_team.h).  What a model-based controller reads off the reference's `sim.data` -- qM (mj_fullM), qfrc_bias,
  * qfrc_gravcomp, mj_jac of the TCP -- and what the reference's hardware driver takes from libfranka every cycle (model.mass, coriolis,

@@ -21,6 +21,7 @@
 #include "render.h"
 #include "query_team.h"
 #include "clearance_team.h"
+#include "swept_team.h"
 #include "dynamics_team.h"
 #include "guard_team.h"
 #include "episode_team.h"
@@ -1428,6 +1429,110 @@ int rcsh_env_clearance_dev(rcsh_sim* s, int32_t kinds, const uint8_t* pair_mask_
   if (!distance_dev) return fail(RCSH_ERR_ARG, "null argument");
   return clearance_dev(s, query_pairs(s, kinds, false), nullptr, nullptr, s->n, kinds, pair_mask_dev, d_max, ClearOut{distance_dev, status_dev, pair_dev, witness_dev, grad_dev},
                        s->S.get(), env_clearance_box_field(s, kinds));
+}
+
+// ---- swept clearance (csrc/swept_team.h)
+namespace {
+int swept_check(rcsh_sim* s, int32_t m, int32_t kinds, const double* free_qpos, double d_max, double tolerance, double resolution) {
+  int rc = clearance_check(s, m, kinds, free_qpos, d_max);
+  if (rc) return rc;
+  if (!(tolerance > 0.0) || !std::isfinite(tolerance)) return fail(RCSH_ERR_ARG, "tolerance must be positive and finite");
+  if (!(resolution > 0.0) || !std::isfinite(resolution)) return fail(RCSH_ERR_ARG, "resolution must be positive and finite");
+  return RCSH_OK;
+}
+// device pointers in; S non-null: the environments' own rows are the segments' starts (m = n_envs)
+int swept_dev(rcsh_sim* s, const QueryPairs& pairs, const double* q_from, const double* q_to, const double* free_qpos, int32_t m, int32_t kinds,
+              const uint8_t* pair_mask, double d_max, double tolerance, double resolution, const rcsh_swept_out& o, const double* S, int box_field) {
+  if (s->cgeoms.empty()) {
+    hipLaunchKernelGGL(k_clearance_fill, dim3((m + 63) / 64), dim3(64), 0, s->stream, o.distance, o.status, o.pair, o.witness, o.grad, d_max, m, s->nl);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_swept_fill, dim3((m + 63) / 64), dim3(64), 0, s->stream, o.lower, o.s, o.evals, d_max, m);
+    HIP_TRY(hipGetLastError());
+    return RCSH_OK;
+  }
+  SweptArgs A{};
+  A.C.Q = query_args(s, m, kinds, pairs);
+  A.C.Q.q0 = q_from; A.C.Q.q1 = q_to; A.C.Q.free_qpos = free_qpos; A.C.Q.resolution = resolution;
+  A.C.pair_mask = pair_mask; A.C.d_max = d_max;
+  A.C.distance = o.distance; A.C.status = o.status; A.C.pair = o.pair; A.C.witness = o.witness; A.C.grad = o.grad;
+  A.C.S = S; A.C.qpos_field = field_of(s, "qpos"); A.C.box_field = box_field;
+  A.tolerance = tolerance; A.lower = o.lower; A.s = o.s; A.evals = o.evals;
+  return team_launch(s, m, "swept clearance", [&](auto topo, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(k_swept_clearance<decltype(topo)>, grid, block, 0, s->stream, A);
+  });
+}
+// the host form of both queries: q_from null: the environments' own rows
+int swept_host(rcsh_sim* s, const double* q_from, const double* q_to, const double* free_qpos, int32_t m, int32_t kinds, const uint8_t* pair_mask,
+               double d_max, double tolerance, double resolution, const rcsh_swept_out& o, const double* S, int box_field) {
+  const size_t nl = (size_t)s->nl, n = (size_t)m;
+  const QueryPairs pairs = query_pairs(s, kinds, pair_mask != nullptr);
+  const size_t nmask = pair_mask ? (size_t)pairs.count() : 0;
+  void* const host[8] = {o.distance, o.lower, o.s, o.pair, o.witness, o.grad, o.evals, o.status};
+  const size_t bytes[8] = {8 * n, 8 * n, 8 * n, 8 * n, 8 * n * 6, 8 * n * nl, 4 * n, n};
+  QuerySlices c;
+  const size_t oa = c.take(q_from ? 8 * n * nl : 0), ob = c.take(8 * n * nl), of = c.take(free_qpos ? 8 * n * 7 : 0), om = c.take(nmask);
+  size_t oo[8];
+  for (int k = 0; k < 8; ++k) oo[k] = c.take(host[k] ? bytes[k] : 0);
+  int rc = grow_device(s, s->d_query, c.total);
+  if (rc) return rc;
+  char* d = static_cast<char*>(s->d_query.p.get());
+  if (q_from) HIP_TRY(hipMemcpyAsync(d + oa, q_from, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(d + ob, q_to, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
+  if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
+  if (nmask) HIP_TRY(hipMemcpyAsync(d + om, pair_mask, nmask, hipMemcpyHostToDevice, s->stream));
+  void* dev[8];
+  for (int k = 0; k < 8; ++k) dev[k] = host[k] ? d + oo[k] : nullptr;
+  const rcsh_swept_out od{static_cast<double*>(dev[0]), static_cast<double*>(dev[1]), static_cast<double*>(dev[2]), static_cast<int32_t*>(dev[3]),
+                          static_cast<double*>(dev[4]), static_cast<double*>(dev[5]), static_cast<int32_t*>(dev[6]), static_cast<uint8_t*>(dev[7])};
+  rc = swept_dev(s, pairs, q_from ? reinterpret_cast<const double*>(d + oa) : nullptr, reinterpret_cast<const double*>(d + ob),
+                 free_qpos ? reinterpret_cast<const double*>(d + of) : nullptr, m, kinds, nmask ? reinterpret_cast<const uint8_t*>(d + om) : nullptr,
+                 d_max, tolerance, resolution, od, S, box_field);
+  if (rc) return rc;
+  for (int k = 0; k < 8; ++k)
+    if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RCSH_OK;
+}
+}  // namespace
+
+int rcsh_swept_clearance(rcsh_sim* s, const double* q_from, const double* q_to, const double* free_qpos, int32_t m, int32_t kinds,
+                         const uint8_t* pair_mask, double d_max, double tolerance, double resolution, const rcsh_swept_out* out) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  int rc = swept_check(s, m, kinds, free_qpos, d_max, tolerance, resolution);
+  if (rc) return rc;
+  if (m == 0) return RCSH_OK;
+  if (!q_from || !q_to || !out || !out->distance) return fail(RCSH_ERR_ARG, "null argument");
+  if ((rc = query_finite(q_from, (size_t)m * s->nl, "q_from")) || (rc = query_finite(q_to, (size_t)m * s->nl, "q_to"))) return rc;
+  if (free_qpos && (rc = query_finite(free_qpos, (size_t)m * 7, "free_qpos"))) return rc;
+  return swept_host(s, q_from, q_to, free_qpos, m, kinds, pair_mask, d_max, tolerance, resolution, *out, nullptr, -1);
+}
+int rcsh_swept_clearance_dev(rcsh_sim* s, const double* q_from_dev, const double* q_to_dev, const double* free_qpos_dev, int32_t m, int32_t kinds,
+                             const uint8_t* pair_mask_dev, double d_max, double tolerance, double resolution, const rcsh_swept_out* out_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  int rc = swept_check(s, m, kinds, free_qpos_dev, d_max, tolerance, resolution);
+  if (rc) return rc;
+  if (m == 0) return RCSH_OK;
+  if (!q_from_dev || !q_to_dev || !out_dev || !out_dev->distance) return fail(RCSH_ERR_ARG, "null argument");
+  return swept_dev(s, query_pairs(s, kinds, false), q_from_dev, q_to_dev, free_qpos_dev, m, kinds, pair_mask_dev, d_max, tolerance, resolution, *out_dev,
+                   nullptr, -1);
+}
+int rcsh_env_swept_clearance(rcsh_sim* s, const double* q_to, int32_t kinds, const uint8_t* pair_mask, double d_max, double tolerance,
+                             double resolution, const rcsh_swept_out* out) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  int rc = swept_check(s, s->n, kinds, nullptr, d_max, tolerance, resolution);
+  if (rc) return rc;
+  if (!q_to || !out || !out->distance) return fail(RCSH_ERR_ARG, "null argument");
+  if ((rc = query_finite(q_to, (size_t)s->n * s->nl, "q_to"))) return rc;
+  return swept_host(s, nullptr, q_to, nullptr, s->n, kinds, pair_mask, d_max, tolerance, resolution, *out, s->S.get(), env_clearance_box_field(s, kinds));
+}
+int rcsh_env_swept_clearance_dev(rcsh_sim* s, const double* q_to_dev, int32_t kinds, const uint8_t* pair_mask_dev, double d_max, double tolerance,
+                                 double resolution, const rcsh_swept_out* out_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  int rc = swept_check(s, s->n, kinds, nullptr, d_max, tolerance, resolution);
+  if (rc) return rc;
+  if (!q_to_dev || !out_dev || !out_dev->distance) return fail(RCSH_ERR_ARG, "null argument");
+  return swept_dev(s, query_pairs(s, kinds, false), nullptr, q_to_dev, nullptr, s->n, kinds, pair_mask_dev, d_max, tolerance, resolution, *out_dev,
+                   s->S.get(), env_clearance_box_field(s, kinds));
 }
 
 // ---- dynamics queries (csrc/dynamics_team.h)

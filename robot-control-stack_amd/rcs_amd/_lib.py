@@ -178,6 +178,12 @@ class DynamicsOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("qM", "qfrc_bias", "gravity", "qfrc_gravcomp", "jac", "qfrc_inverse", "qacc")]
 
 
+class SweptOut(C.Structure):
+    """Output pointers of the swept clearance queries (rcsh_swept_out): host arrays, or device addresses for the _dev forms; NULL: not
+    wanted (``distance`` is required)."""
+    _fields_ = [(name, C.c_void_p) for name in ("distance", "lower", "s", "pair", "witness", "grad", "evals", "status")]
+
+
 # every symbol include/rcs_hip.h declares; load() fails if one is missing
 EXPORTS = (
     "rcsh_last_error", "rcsh_abi_version", "rcsh_device_count", "rcsh_sim_create", "rcsh_sim_destroy",
@@ -208,6 +214,7 @@ EXPORTS = (
     "rcsh_sim_contact_overflow",
     "rcsh_collision_query", "rcsh_collision_query_dev", "rcsh_motion_query", "rcsh_motion_query_dev",
     "rcsh_clearance_pairs", "rcsh_clearance_query", "rcsh_clearance_query_dev", "rcsh_env_clearance", "rcsh_env_clearance_dev",
+    "rcsh_swept_clearance", "rcsh_swept_clearance_dev", "rcsh_env_swept_clearance", "rcsh_env_swept_clearance_dev",
     "rcsh_dynamics_query", "rcsh_dynamics_query_dev", "rcsh_env_dynamics", "rcsh_env_dynamics_dev",
     "rcsh_env_configure_guard", "rcsh_env_guard_peek", "rcsh_env_guard_peek_dev", "rcsh_env_guard_last", "rcsh_env_guard_last_dev",
     "rcsh_env_configure_autoreset", "rcsh_env_autoreset_record_dev", "rcsh_env_autoreset_last", "rcsh_autoreset_draw",
@@ -297,6 +304,10 @@ def load() -> C.CDLL:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_double] + [C.c_void_p] * 5
     for fn in (L.rcsh_env_clearance, L.rcsh_env_clearance_dev):
         fn.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double] + [C.c_void_p] * 5
+    for fn in (L.rcsh_swept_clearance, L.rcsh_swept_clearance_dev):
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.c_void_p] + [C.c_double] * 3 + [C.POINTER(SweptOut)]
+    for fn in (L.rcsh_env_swept_clearance, L.rcsh_env_swept_clearance_dev):
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p] + [C.c_double] * 3 + [C.POINTER(SweptOut)]
     for fn in (L.rcsh_dynamics_query, L.rcsh_dynamics_query_dev):
         fn.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.POINTER(DynamicsOut)]
     for fn in (L.rcsh_env_dynamics, L.rcsh_env_dynamics_dev):

@@ -192,6 +192,37 @@ class VecSimEnv:
         _lib.check(self._L.rcsh_env_clearance_dev(self.sim._h, kinds, p(pair_mask_dev), float(d_max), p(distance_dev), p(status_dev),
                                                   p(pair_dev), p(witness_dev), p(grad_dev)))
 
+    # ---- swept clearance (csrc/swept_team.h): on demand, not part of step
+    def swept_clearance(self, q_to, tolerance: float = 1e-3, resolution: float = 1e-3, d_max: float = np.inf, kinds: int | None = None,
+                        pair_mask=None) -> dict:
+        """How close does every environment come to anything on the straight joint-space motion from where it is now to ``q_to``
+        [N, nl] (the free body standing still at its own pose)?  Arguments and the returned dict as
+        :meth:`rcs_amd.sim.SimRobot.swept_clearance` (``kinds`` None: every kind).  Reads the state, writes none of it."""
+        n, nl = self.n_envs, int(self.sim.model.nq)
+        kinds = sim.SimRobot.COLLISION_ALL if kinds is None else int(kinds)
+        rows = np.ascontiguousarray(np.broadcast_to(np.asarray(q_to, dtype=np.float64), (n, nl)))
+        mask = None
+        if pair_mask is not None:
+            mask = np.ascontiguousarray(pair_mask, dtype=np.uint8).reshape(-1)
+            count = C.c_int32(0)
+            _lib.check(self._L.rcsh_clearance_pairs(self.sim._h, kinds, None, 0, C.byref(count)))
+            if mask.shape[0] != count.value:
+                raise ValueError(f"pair_mask has {mask.shape[0]} entries, the pair list for kinds={kinds} has {count.value}")
+        arrays, out = self.robot._swept_buffers(n, nl)
+        _lib.check(self._L.rcsh_env_swept_clearance(self.sim._h, _lib.ptr(rows), kinds, _lib.ptr(mask), float(d_max), float(tolerance),
+                                                    float(resolution), C.byref(out)))
+        return arrays
+
+    def swept_clearance_dev(self, q_to_dev: int, out: dict, tolerance: float = 1e-3, resolution: float = 1e-3, d_max: float = np.inf,
+                            kinds: int | None = None, pair_mask_dev: int = 0) -> None:
+        """:meth:`swept_clearance` into device buffers, enqueued on the Sim's stream without a synchronisation.  ``q_to_dev``: device
+        address of the [N, nl] ends; ``out``: device addresses by output name (``distance`` is required; absent or 0: not wanted);
+        ``pair_mask_dev``: device address of the mask bytes, 0 for every pair."""
+        kinds = sim.SimRobot.COLLISION_ALL if kinds is None else int(kinds)
+        o = _lib.SweptOut(**{k: int(v) for k, v in out.items() if v})
+        _lib.check(self._L.rcsh_env_swept_clearance_dev(self.sim._h, C.c_void_p(q_to_dev), kinds, C.c_void_p(pair_mask_dev) if pair_mask_dev else None,
+                                                        float(d_max), float(tolerance), float(resolution), C.byref(o)))
+
     # ---- dynamics (csrc/dynamics_team.h): on demand, not part of step
     def dynamics(self, want=None, qacc=None, qfrc=None, tcp_offset=None) -> dict:
         """Every environment's joint-space inertia, bias forces and TCP Jacobian where it is now: its own chain ``qpos`` and ``qvel``.

@@ -639,6 +639,42 @@ class SimRobot:
                                                 _lib.ptr(dist), _lib.ptr(status), _lib.ptr(pair), _lib.ptr(wit), _lib.ptr(grad)))
         return dist, status, pair, wit, grad
 
+    def _swept_buffers(self, m: int, nl: int, want_grad: bool = True):
+        arrays = {"distance": np.zeros(m), "lower": np.zeros(m), "s": np.zeros(m), "pair": np.full((m, 2), -1, dtype=np.int32),
+                  "witness": np.zeros((m, 6)), "evals": np.zeros(m, dtype=np.int32), "status": np.zeros(m, dtype=np.uint8)}
+        if want_grad:
+            arrays["grad"] = np.zeros((m, nl))
+        return arrays, _lib.SweptOut(**{k: a.ctypes.data for k, a in arrays.items()})
+
+    def swept_clearance(self, q_from, q_to, tolerance: float = 1e-3, resolution: float = 1e-3, d_max: float = np.inf, free_qpos=None,
+                        kinds: int = COLLISION_ALL, pair_mask=None, finger_qpos=None, want_grad: bool = True) -> dict:
+        """How close does the robot come to anything along each straight joint-space segment q_from -> q_to, where along it, and to
+        what?  Rows, ``free_qpos``, ``kinds`` and ``finger_qpos`` as ``check_motion``; ``pair_mask`` and ``d_max`` as
+        ``check_clearance``; ``tolerance`` (m): the bracket width asked for; ``resolution`` as ``check_motion``.
+
+        Returns a dict of arrays: ``distance`` [M] -- the smallest clearance found, the point query's answer at q(``s``) --, ``lower``
+        [M] -- a PROVEN lower bound of the clearance over the whole segment (the levers of the motion certificate) --, ``s`` [M],
+        ``pair`` [M, 2], ``witness`` [M, 6], ``grad`` [M, nl] (``check_clearance``'s, at q(s)), ``evals`` [M] int32 and ``status`` [M]
+        uint8: 0 bracketed (distance - lower <= tolerance), 1 nothing comes within d_max anywhere (proven), 2 contact (``s`` is the
+        smallest sampled parameter in contact, as ``check_motion`` finds it; lower = -inf), 3 open (a valid bracket wider than the
+        tolerance; lower = -inf where a finger slide leaves its stroke) (include/rcs_hip.h, rcsh_swept_clearance)."""
+        a = self._query_rows(q_from, finger_qpos, "q_from")
+        b = self._query_rows(q_to, finger_qpos, "q_to")
+        if a.shape != b.shape:
+            raise ValueError(f"q_from {a.shape} and q_to {b.shape} differ")
+        m, nl = a.shape
+        fq = self._free_rows(free_qpos, m)
+        mask = None
+        if pair_mask is not None:
+            mask = np.ascontiguousarray(pair_mask, dtype=np.uint8).reshape(-1)
+            count = len(self.clearance_pairs(kinds))
+            if mask.shape[0] != count:
+                raise ValueError(f"pair_mask has {mask.shape[0]} entries, clearance_pairs({kinds}) lists {count}")
+        arrays, out = self._swept_buffers(m, nl, want_grad)
+        _lib.check(self._L.rcsh_swept_clearance(self.sim._h, _lib.ptr(a), _lib.ptr(b), _lib.ptr(fq), m, int(kinds), _lib.ptr(mask), float(d_max),
+                                                float(tolerance), float(resolution), C.byref(out)))
+        return arrays
+
     # outputs of the dynamics queries, in the order of rcsh_dynamics_out, with the shape of one row
     DYNAMICS_OUTPUTS = ("qM", "qfrc_bias", "gravity", "qfrc_gravcomp", "jac", "qfrc_inverse", "qacc")
 
