@@ -357,11 +357,13 @@ RCSH_D void check_prefetch(const CheckTable& ck, const ContactTable& tab, double
 // gaps it holds are valid lower bounds for a position of this launch (see "the slack" below: the one it began on -- the lean launch --
 // or the one its last substep began on -- the contact-resolving launch, whose collision passes keep the record), keep_slack: the
 // pairs' gaps this check ends with are written back (1: the lean launch; 2: the contact-resolving launch -- both unless the
-// environment is found in contact; 2 also stops looking once every environment of the wavefront is: the answer is all it is asked for).
+// environment is found in contact; 2 also stops looking once every environment of the wavefront is: the answer is all it is asked for;
+// 3: the lean launch of the three-launch step -- as 1, and an environment found in contact has its record moved to the launch's end).
 // known_hit (team-uniform): the caller knows the answer already -- a substep of this launch resolved a contact.  dlo / dhi: how far
 // below / above its value at the launch's end the lane's joint has been (<= 0, >= 0; dend is the larger of the two sizes).  q: the lane's joint position (lane t < NL).  sep: the environment's SEP fields in the state ([8][n], at e).
 // Every lane of the wavefront calls this; returns, on every lane of a team, whether the team's environment is in contact.
-template <class T, class CollT>
+// MOVE (compile time: the lean instantiation of the three-launch step alone carries the code): keep_slack == 3 may be asked for.
+template <class T, bool MOVE = false, class CollT>
 RCSH_D bool unresolved_contact_check(const CheckTable& ck, const ContactTable& tab, const CollT& lc, const LinkRec* links, double* frames,
                                      double* work, double q, bool live, bool check_plane, double sep_in, double* sep, int n_env, const CheckPrefetch& pf,
                                      double dend, double psum, double* mv, double q0, float* slack_env, bool use_slack, int keep_slack, bool known_hit = false,
@@ -999,6 +1001,23 @@ RCSH_D bool unresolved_contact_check(const CheckTable& ck, const ContactTable& t
         if (t + kTeamLanes * j < npair) slack_env[t + kTeamLanes * j] = rem[j];
     }
     if (valid && check_plane) slack_env[kSlackLink + t] = remL;
+  }
+  // keep_slack == 3, the lean launch of the three-launch step (verify_team.h): an environment found in contact here may still keep this
+  // launch's result -- no substep of it touches --, and nobody would then have moved the record to where the launch ENDED.  So it goes
+  // back for that position: a pair that was not due has been charged the launch's whole path, a due pair (looked at or not) and a due
+  // link count as unknown (0: look).  The joints the record holds for become the launch's last ones: the contact-resolving launch, if it
+  // redoes the step from the copy, charges the way back from there (contact_team.h: contact_collide), and the next lean launch reads
+  // the record from there (sim_kernels.h).  The geoms' heights above the floor, which only the collision passes keep and which hold for
+  // the joints they saw last, are unknown from here on.
+  if constexpr (MOVE) {
+    if (keep_slack == 3 && hit && slack_env && live && !(ck.pad & 16)) {
+#pragma unroll
+      for (int j = 0; j < kCheckPer; ++j)
+        if (t + kTeamLanes * j < npair) slack_env[t + kTeamLanes * j] = (due >> j) & 1u ? 0.0f : rem[j];
+      if (valid && check_plane) slack_env[kSlackLink + t] = dueL ? 0.0f : remL;
+      if (valid) reinterpret_cast<double*>(slack_env + kMaxCheckPairs)[t] = q;
+      for (int g = t; g < kSlackLink - kSlackFloor; g += kTeamLanes) slack_env[kSlackFloor + g] = 0.0f;
+    }
   }
   CHK_MARK(6)
   TAIL_END(false)

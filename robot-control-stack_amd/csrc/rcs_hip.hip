@@ -18,6 +18,7 @@
 #include "model_host.h"
 #include "owned.h"
 #include "sim_kernels.h"
+#include "verify_team.h"
 #include "render.h"
 #include "query_team.h"
 #include "clearance_team.h"
@@ -82,6 +83,7 @@ struct Staging {
 // Page-locked staging of the env layer's host forms, between the caller's arrays and the device slices (offsets in bytes):
 // [action | gripper | box pose | obs | info | gripper width | substeps | task]
 struct PinLayout { size_t action, gripper, box, obs, info, gw, sub, task, total; };
+constexpr size_t kEscRows = 4;  // rows of the escalation masks (RunOp::esc)
 // Who owns what: every buffer, stream and event the handle creates lives in an owner (owned.h) below and goes when the handle is
 // deleted -- members in reverse order, so own_stream, declared before every buffer, goes last.  An entry point that replaces or first
 // creates a GROUP of resources builds it in local owners and moves it in after the last step that can fail: on failure the handle
@@ -135,11 +137,12 @@ struct rcsh_sim {
   // the contact-resolving launch over the others
   bool esc_mode = false;
   struct EscBufs {                 // one group, present or absent together (rcsh_sim_set_contact_options)
-    DevBuf<uint64_t> mask;         // [3][(n + 63) / 64]: escalated, newly flagged, leaving
+    DevBuf<uint64_t> mask;         // [kEscRows][(n + 63) / 64]: escalated, newly flagged, leaving, touching (RunOp::esc)
     DevBuf<uint32_t> ctr;          // [4] (sim_kernels.h: RunOp::esc_ctr)
     DevBuf<double> snap;           // [nfields][n]: what the lean launch of a step read (the step is redone from it on a hit)
     DevBuf<uint32_t> snap_flags;
     DevBuf<int32_t> snap_conv;
+    DevBuf<double> trace;          // [kEscTraceCap][nl][n]: where the lean launch's substeps began (RunOp::trace)
   } esc;
   int conv_chunk = 48;              // step_until_convergence in pieces of this many substeps when contacts are resolved per environment (launch_run; RCSH_CONV_CHUNK)
   bool contact_check = true;  // RCSH_CONTACT_CHECK=0 switches the check off (measurements of its cost)
@@ -454,9 +457,21 @@ int launch_run_once(rcsh_sim* s, const RunOp& op_in, bool timed) {
         if (esc) {
           // (the certifying check -- check_team.h -- is the default; RCSH_CHECK_CERTIFY=0: the check of the final position alone, round 5's)
           static const int certify = [] { const char* e = std::getenv("RCSH_CHECK_CERTIFY"); return e ? std::atoi(e) : 1; }();
-          // the lean launch over the environments not escalated, then the contact-resolving launch over the others, one behind the other
+          // Three launches, one behind the other: the lean launch over EVERY environment, which records where each
+          // substep began; the verify launch, the collision passes of the substeps of whoever failed the certificate, side by side; the
+          // contact-resolving launch over the environments one of those passes found touching, each redone from the copy.
+          // RCSH_ESC_VERIFY=0 (read on every launch), launches longer than the trace and step_until_convergence's pieces take the two
+          // launches of before: the lean launch over the environments not escalated, the contact-resolving launch over the others.
+          const char* ev = std::getenv("RCSH_ESC_VERIFY");
+          const int nsub = op.do_reset ? 1 : op.nsteps;
+          const bool verify = !(ev && std::atoi(ev) == 0) && certify && !det && nsub > 0 && nsub <= kEscTraceCap;
+          if (verify) { op.trace = s->esc.trace.get(); op.esc_part = 2; }
           op.esc_role = 1; op.check = certify ? 2 : 1;
           go(N{}, N{}, N{});
+          if (verify) {
+            const char* vm = std::getenv("RCSH_VERIFY_MAX");  // (read on every launch, like RCSH_ESC_VERIFY: the tests switch it)
+            hipLaunchKernelGGL((k_verify_team<T>), dim3(kVerifyGrid), block, 0, s->stream, P, op, nsub, vm ? std::atoi(vm) : kVerifyMaxFlagged);
+          }
           op.esc_role = 2; op.check = certify ? 2 : 0;
           go(N{}, N{}, Y{});
         } else {
@@ -937,14 +952,14 @@ int rcsh_sim_reset(rcsh_sim* s, const uint8_t* mask) {
   if (!rc && s->esc.mask) {
     // per-environment escalation: a reset environment starts over on the lean kernel
     const size_t nw = ((size_t)s->n + 63) / 64;
-    std::vector<uint64_t> w(3 * nw, 0);
+    std::vector<uint64_t> w(kEscRows * nw, 0);
     if (mask) {
       HIP_TRY(hipMemcpyAsync(w.data(), s->esc.mask.get(), sizeof(uint64_t) * nw, hipMemcpyDeviceToHost, s->stream));
       HIP_TRY(hipStreamSynchronize(s->stream));
       for (int e = 0; e < s->n; ++e)
         if (mask[e]) w[e >> 6] &= ~(1ull << (e & 63));
     }
-    HIP_TRY(hipMemcpyAsync(s->esc.mask.get(), w.data(), sizeof(uint64_t) * 3 * nw, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->esc.mask.get(), w.data(), sizeof(uint64_t) * kEscRows * nw, hipMemcpyHostToDevice, s->stream));
     uint32_t ctr[4] = {0, 0, 0, 0};  // (RunOp::esc_ctr: [1] has to say how many are escalated -- a role-2 launch trusts a zero)
     for (size_t i = 0; i < nw; ++i) ctr[1] += (uint32_t)__builtin_popcountll(w[i]);
     HIP_TRY(hipMemcpyAsync(s->esc.ctr.get(), ctr, sizeof(ctr), hipMemcpyHostToDevice, s->stream));
@@ -1833,7 +1848,7 @@ int rcsh_sim_set_contact_options(rcsh_sim* s, const rcsh_contact_options* o) {
   // advisor, round 5)
   if (s->esc.mask) {
     const size_t nw = ((size_t)s->n + 63) / 64;
-    HIP_TRY(hipMemsetAsync(s->esc.mask.get(), 0, sizeof(uint64_t) * 3 * nw, s->stream));
+    HIP_TRY(hipMemsetAsync(s->esc.mask.get(), 0, sizeof(uint64_t) * kEscRows * nw, s->stream));
     HIP_TRY(hipMemsetAsync(s->esc.ctr.get(), 0, sizeof(uint32_t) * 4, s->stream));
     int f_box = -1;
     dispatch_topology(s->narm, s->grip, [&](auto topo) { f_box = (int)Lay<decltype(topo)>::BOX; });
@@ -1851,18 +1866,19 @@ int rcsh_sim_set_contact_options(rcsh_sim* s, const rcsh_contact_options* o) {
   b.present = 0;
   b.resolve = 1 | (o->resolve_robot_contacts & 2);  // (bit 1: contacts between two geoms of the robot too)
   const bool esc_mode = (o->resolve_robot_contacts & 4) != 0;  // (bit 2: environment by environment instead of the whole batch)
-  // what the option needs and the handle does not have yet is built here and attached below, with the option itself: the five
+  // what the option needs and the handle does not have yet is built here and attached below, with the option itself: the six
   // escalation buffers as one group, the slack record as another
   rcsh_sim::EscBufs esc;
   DevBuf<float> slack;
   if (esc_mode && !s->esc.mask) {
     const size_t nw = ((size_t)s->n + 63) / 64;
-    HIP_TRY(hipMalloc(esc.mask.out(), sizeof(uint64_t) * 3 * nw));
+    HIP_TRY(hipMalloc(esc.mask.out(), sizeof(uint64_t) * kEscRows * nw));
     HIP_TRY(hipMalloc(esc.ctr.out(), sizeof(uint32_t) * 4));
     HIP_TRY(hipMalloc(esc.snap.out(), sizeof(double) * (size_t)(s->nfields + kMaxRateCams) * s->n));  // (+ the rate-driven cameras' clocks)
     HIP_TRY(hipMalloc(esc.snap_flags.out(), sizeof(uint32_t) * s->n));
     HIP_TRY(hipMalloc(esc.snap_conv.out(), sizeof(int32_t) * s->n));
-    HIP_TRY(hipMemsetAsync(esc.mask.get(), 0, sizeof(uint64_t) * 3 * nw, s->stream));
+    HIP_TRY(hipMalloc(esc.trace.out(), sizeof(double) * (size_t)kEscTraceCap * s->nl * s->n));
+    HIP_TRY(hipMemsetAsync(esc.mask.get(), 0, sizeof(uint64_t) * kEscRows * nw, s->stream));
     HIP_TRY(hipMemsetAsync(esc.ctr.get(), 0, sizeof(uint32_t) * 4, s->stream));
     HIP_TRY(hipMemsetAsync(esc.snap.get(), 0, sizeof(double) * (size_t)(s->nfields + kMaxRateCams) * s->n, s->stream));
   }
@@ -2009,7 +2025,7 @@ int rcsh_sim_set_state(rcsh_sim* s, const void* blob) {
   if (s->esc.mask) {
     const size_t ne = sizeof(uint64_t) * (((size_t)s->n + 63) / 64);
     HIP_TRY(hipMemcpyAsync(s->esc.mask.get(), b + ns + nf + nc, ne, hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemsetAsync(s->esc.mask.get() + ne / sizeof(uint64_t), 0, 2 * ne, s->stream));
+    HIP_TRY(hipMemsetAsync(s->esc.mask.get() + ne / sizeof(uint64_t), 0, (kEscRows - 1) * ne, s->stream));
     uint32_t ctr[4] = {0, 0, 0, 0};  // (RunOp::esc_ctr[1]: how many are escalated)
     const uint64_t* w = reinterpret_cast<const uint64_t*>(b + ns + nf + nc);
     for (size_t i = 0; i < ne / sizeof(uint64_t); ++i) { uint64_t v; std::memcpy(&v, w + i, sizeof(v)); ctr[1] += (uint32_t)__builtin_popcountll(v); }

@@ -130,20 +130,27 @@ struct RunOp {
                           // cannot clear pairs that are 15 mm apart in every pose, a quarter of it can -- and an environment that fails is
                           // redone for that piece only
   // esc_part / esc_seq / esc_host: what is left of a dropped form of role 2 ("What the round's measurements say", item 7).
-  // The host leaves all three zero: esc_select takes its esc_part == 0 arms and the two blocks that test esc_host never run.  Folding
+  // The host leaves esc_seq and esc_host zero and never sets esc_part to 1: the two blocks that test esc_host never run.  Folding
   // esc_select or deleting those blocks moves the register allocation of some instantiations (SGPR spills; VGPR spills and 16-32 bytes
   // of scratch: profiles/retire_split_regs.txt), so they stay until those kernels are next retuned.
+  // esc_part == 2 has a meaning again -- the three-launch step (verify_team.h): the lean launch steps EVERY
+  // environment (`trace` set), the verify launch runs the collision passes of the substeps of those that fail the certificate, side by
+  // side, and role 2 takes esc[3] ("touch") alone and redoes every member from the copy.
   int32_t esc_part;
   int32_t esc_seq;
   int32_t conv_resume;    // this launch CONTINUES a step_until_convergence begun by an earlier one: substep count, verdicts and the cap carry over
   uint32_t* esc_host;
-  uint64_t* esc;          // [3][(n + 63) / 64]
+  uint64_t* esc;          // [4][(n + 63) / 64]: escalated, failed this step's certificate ("new"), leave, touch (esc_part == 2)
   uint32_t* esc_ctr;      // [0] workgroups of the role-2 launch that are done, [1] environments escalated after the last merge,
-                          // [2] environments the role-1 launch of this step has flagged (a role-2 launch that finds [1] = [2] = 0 ends at once)
+                          // [2] environments the role-1 launch of this step has flagged (a role-2 launch that finds [1] = [2] = 0 ends at once),
+                          // [3] the three-launch step: environments the verify launch of this step has put into esc[3] (zeroed by its lean launch)
   double* snap;           // [Lay::COUNT][n]
   uint32_t* snap_flags;   // [n]
   int32_t* snap_conv;     // [n]
+  double* trace;          // [kEscTraceCap][NL][n] the three-launch step: the joint positions every substep of the lean launch began on
+                          // (row k: substep k); null: the two-launch step
 };
+constexpr int kEscTraceCap = 48;  // substeps a launch of the three-launch step may have: Sim.step's 17, a conv_chunk piece; longer launches take two
 
 // inclusive prefix sum over the 64 lanes of the wavefront
 __device__ __forceinline__ int wave_incl_scan(int x) {
@@ -170,7 +177,8 @@ __device__ __forceinline__ int esc_select(const RunOp& op, int n, int r0, int te
   const int lane = (int)(threadIdx.x & 63u);
   const int nw = (n + 63) >> 6;
   const uint64_t* A = op.esc;
-  const uint64_t* B = op.esc + nw;
+  // (esc_part == 2, the three-launch step: role 2's set is the "touch" row alone, and every member is redone from the copy)
+  const uint64_t* B = op.esc + (op.esc_part == 2 ? 3 * nw : nw);
   int result = -1, base = 0, per = 4;
   redo = false;
   if (spread) {
@@ -206,7 +214,7 @@ __device__ __forceinline__ int esc_select(const RunOp& op, int n, int r0, int te
       const int bit = __ffsll((long long)wl) - 1;
       if (team == k) {
         result = (c0 + L) * 64 + bit;
-        redo = op.esc_role == 2 && !((wave_read_u64(a, L) >> bit) & 1ull);
+        redo = op.esc_role == 2 && (op.esc_part == 2 || !((wave_read_u64(a, L) >> bit) & 1ull));
       }
     }
     base += total;
@@ -216,6 +224,7 @@ __device__ __forceinline__ int esc_select(const RunOp& op, int n, int r0, int te
 }
 // role 2, at the very end of a workgroup: the last one to finish merges the masks (nobody reads them any more: the next launch of the
 // stream starts after this one has ended)
+__device__ __forceinline__ void esc_merge(const RunOp& op, int n);
 __device__ __forceinline__ void esc_finish(const RunOp& op, int n) {
   __threadfence();
   int last = 0;
@@ -223,6 +232,10 @@ __device__ __forceinline__ void esc_finish(const RunOp& op, int n) {
   last = __builtin_amdgcn_readfirstlane(last);
   if (!last) return;
   __threadfence();
+  esc_merge(op, n);
+}
+// the merge itself, by one wavefront once nobody else reads the masks
+__device__ __forceinline__ void esc_merge(const RunOp& op, int n) {
   const int nw = (n + 63) >> 6;
   int count = 0;
   for (int wi = (int)(threadIdx.x & 63u); wi < nw; wi += 64) {
@@ -231,6 +244,7 @@ __device__ __forceinline__ void esc_finish(const RunOp& op, int n) {
     op.esc[wi] = a;
     op.esc[nw + wi] = 0;
     op.esc[2 * nw + wi] = 0;
+    op.esc[3 * nw + wi] = 0;
     count += __popcll(a);
   }
   count = wave_incl_scan(count);
@@ -733,6 +747,16 @@ __device__ __attribute__((always_inline)) inline void run_team_body(const Params
   if constexpr (CON) {
     if (opk.esc_role == 2 && opk.esc_ctr[1] == 0 && opk.esc_ctr[2] == 0) return;
   }
+  // (the three-launch step, the verify launch found nobody touching -- every step in which the marked environments are all quiet:
+  // nothing to redo, only the masks to merge, which workgroup 0 does on its own; the others end before a load has gone out.  With every
+  // workgroup ranking the empty row first the launch took 20-23 us instead of the empty launch's 4.6:
+  // profiles/substep_verify/trace.txt.  Nobody writes esc_ctr[3] during this launch.)
+  if constexpr (CON && !BOX && !FRIC && !DET) {
+    if (opk.esc_role == 2 && opk.esc_part == 2 && opk.esc_ctr[3] == 0) {
+      if (blockIdx.x == 0) esc_merge(opk, Pk.n);
+      return;
+    }
+  }
   LdsCopy<sizeof(Params) / 8> cp_params;
   LdsCopy<sizeof(RunOp) / 8> cp_op;
   LdsCopy<sizeof(DevModelHead) / 8> cp_head;
@@ -846,8 +870,17 @@ __device__ __attribute__((always_inline)) inline void run_team_body(const Params
     __syncthreads();
   }
   TEAM_MARK(12)
-  const bool live = in_range && !((esc_word >> (e & 63)) & 1ull);
+  // (the three-launch step, RunOp::trace: nobody sits out -- an escalated environment is stepped here like the others, and redone by the
+  // contact-resolving launch only if one of its substeps turns out to touch)
+  // (the instantiations the three-launch step's lean launch runs: the archetype whose robot contacts are resolved, rcs_hip.hip)
+  constexpr bool kTrace = !FRIC && !BOX && !CON && !DET && T::NARM == 7 && T::GRIP;
+  const bool live = in_range && (!((esc_word >> (e & 63)) & 1ull) || (kTrace && opk.trace != nullptr));
   const bool leader = t == 0 && live;
+  if constexpr (kTrace) {
+    // (the count of touching environments the verify launch of this step keeps, RunOp::esc_ctr[3], starts at zero: nobody reads it
+    // before that launch)
+    if (esc_role == 1 && opk.trace && blockIdx.x == 0 && threadIdx.x == 0) opk.esc_ctr[3] = 0;
+  }
   if (esc_role == 1 && __ballot(live) == 0) {  // (every environment of this workgroup is on the contact-resolving kernel, or out of range)
     if (blockIdx.x == 0 && threadIdx.x == 0 && opk.esc_host) {  // (never taken: RunOp::esc_host)
       __hip_atomic_store(opk.esc_host + 1, opk.esc_ctr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1036,8 +1069,43 @@ __device__ __attribute__((always_inline)) inline void run_team_body(const Params
   // contact that begins AND ends inside the launch needs the geoms to cover their gaps on the way)
   double chk_qmin = 0.0, chk_qmax = 0.0, chk_q0 = 0.0;
   bool chk_first = true;
+  // the three-launch step: where the lane's joint stands at the top of every substep goes to the trace (verify_team.h reads it); the
+  // host takes this path for launches of at most kEscTraceCap substeps
+  double* trace_row = nullptr;
+  bool rec_unanchored = false;  // (team-uniform) the environment's record of remaining gaps is not read by this launch's check
+  if constexpr (kTrace) {
+    if (esc_role == 1 && op.trace && live && t < T::NL) trace_row = op.trace + (size_t)t * P.n + e;
+    // An environment that failed the last step's certificate: its record of remaining gaps (check_team.h: "the slack") holds for the
+    // joints kept with it, not for where this launch begins -- if the contact-resolving launch redid that step, its collision passes
+    // left the record where its last SUBSTEP began; if nobody did, the lean launch's check left it, and the joints with it, where that
+    // launch ended.  The joints' path over this launch begins there: the certificate then charges the way from there as well.
+    // (A record that a state write has voided -- rcs_hip.hip: void_remembered_gaps -- is zero throughout, joints included: it claims
+    // nothing, so there is nowhere to charge from.  Joints that are all exactly 0.0 are taken for that, and the check below is then
+    // given NO record for the environment -- every pair and link is looked at --, so a record that really stands at the all-zero pose
+    // is not trusted from the wrong place either: it is only not used.)
+    const bool carried = esc_role == 1 && op.trace && op.check == 2 && live && t < T::NL && lp.chk.slack && ((esc_word >> (e & 63)) & 1ull);
+    double qp = 0.0, wp = 0.0;
+    if (carried) {
+      const double* qpg = reinterpret_cast<const double*>(lp.chk.slack + (size_t)e * kSlackStride + kMaxCheckPairs);
+      qp = qpg[t];
+      wp = qp;
+      if (T::GRIP && t >= T::NARM) wp = t == T::NARM ? qpg[T::NARM] + qpg[T::NARM + 1] : qpg[T::NARM] - qpg[T::NARM + 1];
+    }
+    const bool anchored = team_ballot(carried && qp != 0.0) != 0;
+    if (anchored && carried) {
+      chk_q0 = qp; chk_qmin = wp; chk_qmax = wp;
+      chk_first = false;
+    }
+    rec_unanchored = team_ballot(carried) != 0 && !anchored;
+  }
   while (going) {
     const bool stepping = (going >> (threadIdx.x & 48)) & 1u;
+    if constexpr (kTrace) {
+      if (trace_row && stepping) {
+        *trace_row = st.q(t);
+        trace_row += (size_t)T::NL * P.n;
+      }
+    }
     if (op.check == 2 && t < T::NL) {
       const double qn = st.q(t);
       chk_q0 = chk_first ? qn : chk_q0;
@@ -1315,7 +1383,7 @@ __device__ __attribute__((always_inline)) inline void run_team_body(const Params
   // launch's path, which is all the check's slack test asks for; round 6 first looked at every pair there, 300-500k cycles of every
   // escalated environment's launch, a quarter of a quiet one's)
   const bool chk_use_slack = esc_role != 0 && !op.do_reset && op.check == 2;
-  if (do_check) check_prefetch(lp.chk, lp.ctab, sep_in, live, chk_pf, chk_use_slack ? chk_slack : nullptr);
+  if (do_check) check_prefetch(lp.chk, lp.ctab, sep_in, live, chk_pf, chk_use_slack && !(kTrace && rec_unanchored) ? chk_slack : nullptr);
   {
     // per-component stores of the epilogue, one per lane instead of a dozen from the leader: the site link's frame of the last
     // position stage, the joints of the observation row
@@ -1437,8 +1505,8 @@ __device__ __attribute__((always_inline)) inline void run_team_body(const Params
 #ifdef RCSH_WAVE_TIMES
     wt2_ = __builtin_amdgcn_s_memrealtime();
 #endif
-    const bool hit = unresolved_contact_check<T>(lp.chk, lp.ctab, lp.coll, llinks, reinterpret_cast<double*>(&llinks[0]), check_work, q_final, checked, chk_plane, sep_in, sep, P.n, chk_pf,
-                                                 chk_dend, chk_psum, check_mv, chk_first ? q_final : chk_q0, esc_role != 0 ? chk_slack : nullptr, chk_use_slack, op.check == 2 ? esc_role : 0,
+    const bool hit = unresolved_contact_check<T, kTrace>(lp.chk, lp.ctab, lp.coll, llinks, reinterpret_cast<double*>(&llinks[0]), check_work, q_final, checked, chk_plane, sep_in, sep, P.n, chk_pf,
+                                                 chk_dend, chk_psum, check_mv, chk_first ? q_final : chk_q0, esc_role != 0 ? chk_slack : nullptr, chk_use_slack, op.check == 2 ? (kTrace && esc_role == 1 && lop.trace ? 3 : esc_role) : 0,
                                                  CON && esc_role == 2 && team_ballot(esc_contact) != 0, chk_dlo, chk_dhi);
 #ifdef RCSH_CHECK_DEBUG
     if (leader) { atomicAdd(&g_chk_dbg[34], hit ? 1 : 0); atomicAdd(&g_chk_dbg[37], 1); }
@@ -1448,6 +1516,12 @@ __device__ __attribute__((always_inline)) inline void run_team_body(const Params
       if (leader && hit) {
         atomicOr(reinterpret_cast<unsigned long long*>(lop.esc + ((P.n + 63) >> 6) + (e >> 6)), 1ull << (e & 63));
         atomicAdd(lop.esc_ctr + 2, 1u);
+      }
+      if constexpr (kTrace) {
+        // the three-launch step: an escalated environment this launch certifies goes back -- role 2's leave rule, "no contact and
+        // certified", and certified implies no contact (the word is asked for again here: nobody has written the row since the prologue)
+        if (leader && !hit && have_frames && lop.trace && ((lop.esc[e >> 6] >> (e & 63)) & 1ull))
+          atomicOr(reinterpret_cast<unsigned long long*>(lop.esc + 2 * ((P.n + 63) >> 6) + (e >> 6)), 1ull << (e & 63));
       }
     } else if (esc_role == 2) {
       // Back to the lean launch: an environment none of whose substeps met a contact AND whose launch passes the lean launch's own
