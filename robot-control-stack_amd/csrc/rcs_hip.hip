@@ -17,6 +17,7 @@
 #include "../../include/rcs_hip.h"
 #include "model_host.h"
 #include "owned.h"
+#include "host_stage.h"
 #include "sim_kernels.h"
 #include "verify_team.h"
 #include "render.h"
@@ -116,7 +117,7 @@ struct rcsh_sim {
   GrownDev d_pairs, d_chk_ent, d_chk_geoms;  // SelfPair[], CheckEntry[], CheckGeom[]
   DevBuf<float> d_lev;               // tables.link_lever
   DevBuf<float> d_slack;             // [n][kSlackStride]: the self-contact stage's remaining gaps per pair + the joints it saw last (CheckTable::slack)
-  GrownDev d_query;                  // staging of the host-pointer collision queries (rcsh_collision_query / rcsh_motion_query) and of the peek's action
+  GrownDev d_query;                  // staging of every host-pointer query form (staged_call): point, motion, clearance, swept clearance, dynamics, and the peek's action
   // the environments' collision guard (guard_team.h; rcsh_env_configure_guard): its settings, and two records of [result | t_contact |
   // blocked | hold] -- the last guarded step's (rcsh_env_guard_last) and the scratch of rcsh_env_guard_peek.  d_guard and h_guard are
   // one group, present or absent together; so are d_episode and h_episode below.
@@ -184,7 +185,7 @@ struct rcsh_sim {
   const double* frames_src_base(int slot) const { return rend.snap + (size_t)slot * (size_t)(nl + 9) * (size_t)n; }
   bool render_f64 = false;      // the ray caster's arithmetic type (rcsh_sim_set_render_f64; RCSH_RENDER_F64=1 at creation)
   std::vector<RenderCam> cams;
-  GrownDev d_image;  // staging for the host-pointer render call
+  GrownDev d_image;  // staging of the host-pointer render call (staged_call)
   double* pending_task = nullptr;  // view into the caller's memory or the staging: task output of the env-step being enqueued (rcsh_env_step_task*)
   // staging for the host-pointer entry points: the device side, fixed at creation (stage_create), and page-locked memory between it and
   // the caller's arrays for the env layer's host forms (PinLayout; a copy to or from pageable memory is staged by the runtime and waited
@@ -300,6 +301,23 @@ int grow(rcsh_sim* s, G& g, size_t bytes, Alloc alloc) {
 }
 int grow_device(rcsh_sim* s, GrownDev& g, size_t bytes) { return grow(s, g, bytes, [](void** p, size_t b) { return hipMalloc(p, b); }); }
 int grow_pinned(rcsh_sim* s, GrownPin& g, size_t bytes) { return grow(s, g, bytes, [](void** p, size_t b) { return hipHostMalloc(p, b, hipHostMallocDefault); }); }
+
+// One host-pointer call over a grown device buffer, laid out by a StageLayout (host_stage.h): declare once, view after grow, one wait.
+// Grows `g` to the layout's total, enqueues the uploads of the present inputs, runs `body` -- the launches --, enqueues the downloads
+// of the outputs asked for and waits for the stream: the call's one wait.  Device views exist only as `dev(ticket)` of the function
+// that `body` is handed, so none can be taken before the grow, which may free and reallocate.
+template <class Body>
+int staged_call(rcsh_sim* s, GrownDev& g, const StageLayout& L, Body body) {
+  if (int rc = grow_device(s, g, L.total)) return rc;
+  char* const base = static_cast<char*>(g.p.get());
+  for (int i = 0; i < L.count; ++i)
+    if (const auto& e = L.slice[i]; e.src) HIP_TRY(hipMemcpyAsync(base + e.at, e.src, e.bytes, hipMemcpyHostToDevice, s->stream));
+  if (int rc = body([&](auto ticket) { return L.view(base, ticket); })) return rc;
+  for (int i = 0; i < L.count; ++i)
+    if (const auto& e = L.slice[i]; e.dst) HIP_TRY(hipMemcpyAsync(e.dst, e.from ? e.from : base + e.at, e.bytes, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RCSH_OK;
+}
 
 // a host table's device copy; the buffer grows on demand (grow_device waits for the stream before it frees one a launch may still read)
 int upload(rcsh_sim* s, GrownDev& g, const void* src, size_t bytes) {
@@ -529,6 +547,7 @@ int field_of(rcsh_sim* s, const char* name) {
 // ---- staging of the host-pointer entry points
 constexpr int kStageWidth = 48;  // doubles per environment of the widest field group (the free body's state)
 constexpr int kInfoBytes = 8, kPoseWidth = 7, kTaskWidth = 9, kObsBase = 14;  // info row; pose; task row = box pose + reward + terminated; observation = kObsBase + narm
+constexpr int kPairWidth = 2, kWitnessWidth = 6, kJacRows = 6, kCamPoseWidth = 12, kRgbWidth = 3;  // geom ids of a pair; two witness points; rows of the TCP Jacobian; camera xmat + xpos; bytes of a pixel
 static_assert(kBoxState <= kStageWidth, "the free body's state passes through the staging buffer in one piece");
 static_assert(kPoseWidth <= kTaskWidth, "the box pose comes in through the task rows' slice");
 static_assert(kPoseWidth <= kObsBase, "a forward-kinematics pose goes out through the observations' slice");
@@ -1226,12 +1245,6 @@ int query_launch(rcsh_sim* s, const QueryArgs& A, bool motion) {
     else hipLaunchKernelGGL(k_collision_query<T>, grid, block, 0, s->stream, A);
   });
 }
-// Device staging of the host-pointer query forms: slices cut out of d_query in the order they are taken (offsets in bytes, every slice
-// 8-byte aligned; an absent array takes none)
-struct QuerySlices {
-  size_t total = 0;
-  size_t take(size_t bytes) { const size_t at = total; total += align8(bytes); return at; }
-};
 // device pointers in: the answer for a robot without collision geometry is written without a kernel
 int point_query_dev(rcsh_sim* s, const double* q, const double* free_qpos, int32_t m, int32_t kinds, uint8_t* hit, uint8_t* kinds_hit,
                     int32_t* pair) {
@@ -1276,21 +1289,13 @@ int rcsh_collision_query(rcsh_sim* s, const double* q, const double* free_qpos, 
   if (!q || !hit) return fail(RCSH_ERR_ARG, "null argument");
   const size_t nl = (size_t)s->nl, n = (size_t)m;
   if ((rc = query_finite(q, n * nl, "q"))) return rc;
-  if (free_qpos && (rc = query_finite(free_qpos, n * 7, "free_qpos"))) return rc;
-  QuerySlices c;
-  const size_t oq = c.take(8 * n * nl), of = c.take(free_qpos ? 8 * n * 7 : 0), oh = c.take(n), ok = c.take(n), op = c.take(8 * n);
-  if ((rc = grow_device(s, s->d_query, c.total))) return rc;
-  char* d = static_cast<char*>(s->d_query.p.get());
-  HIP_TRY(hipMemcpyAsync(d + oq, q, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
-  if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
-  rc = point_query_dev(s, reinterpret_cast<const double*>(d + oq), free_qpos ? reinterpret_cast<const double*>(d + of) : nullptr, m, kinds,
-                       reinterpret_cast<uint8_t*>(d + oh), reinterpret_cast<uint8_t*>(d + ok), reinterpret_cast<int32_t*>(d + op));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(hit, d + oh, n, hipMemcpyDeviceToHost, s->stream));
-  if (kinds_hit) HIP_TRY(hipMemcpyAsync(kinds_hit, d + ok, n, hipMemcpyDeviceToHost, s->stream));
-  if (pair) HIP_TRY(hipMemcpyAsync(pair, d + op, 8 * n, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return RCSH_OK;
+  if (free_qpos && (rc = query_finite(free_qpos, n * kPoseWidth, "free_qpos"))) return rc;
+  StageLayout L;
+  const auto dq = L.in(q, n * nl), df = L.in(free_qpos, n * kPoseWidth);
+  // (the kernel is handed all three outputs whatever the caller asked for, as in the clearance form)
+  const auto dh = L.out_always(hit, n), dk = L.out_always(kinds_hit, n);
+  const auto dp = L.out_always(pair, n * kPairWidth);
+  return staged_call(s, s->d_query, L, [&](auto dev) { return point_query_dev(s, dev(dq), dev(df), m, kinds, dev(dh), dev(dk), dev(dp)); });
 }
 int rcsh_collision_query_dev(rcsh_sim* s, const double* q_dev, const double* free_qpos_dev, int32_t m, int32_t kinds, uint8_t* hit_dev,
                              uint8_t* kinds_hit_dev, int32_t* pair_dev) {
@@ -1310,22 +1315,12 @@ int rcsh_motion_query(rcsh_sim* s, const double* q_from, const double* q_to, con
   if (!q_from || !q_to || !result || !t_contact) return fail(RCSH_ERR_ARG, "null argument");
   const size_t nl = (size_t)s->nl, n = (size_t)m;
   if ((rc = query_finite(q_from, n * nl, "q_from")) || (rc = query_finite(q_to, n * nl, "q_to"))) return rc;
-  if (free_qpos && (rc = query_finite(free_qpos, n * 7, "free_qpos"))) return rc;
-  QuerySlices c;
-  const size_t oa = c.take(8 * n * nl), ob = c.take(8 * n * nl), of = c.take(free_qpos ? 8 * n * 7 : 0), orr = c.take(4 * n), ot = c.take(8 * n);
-  if ((rc = grow_device(s, s->d_query, c.total))) return rc;
-  char* d = static_cast<char*>(s->d_query.p.get());
-  HIP_TRY(hipMemcpyAsync(d + oa, q_from, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(d + ob, q_to, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
-  if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
-  rc = motion_query_dev(s, reinterpret_cast<const double*>(d + oa), reinterpret_cast<const double*>(d + ob),
-                        free_qpos ? reinterpret_cast<const double*>(d + of) : nullptr, m, kinds, resolution, reinterpret_cast<int32_t*>(d + orr),
-                        reinterpret_cast<double*>(d + ot));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(result, d + orr, 4 * n, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(t_contact, d + ot, 8 * n, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return RCSH_OK;
+  if (free_qpos && (rc = query_finite(free_qpos, n * kPoseWidth, "free_qpos"))) return rc;
+  StageLayout L;
+  const auto da = L.in(q_from, n * nl), db = L.in(q_to, n * nl), df = L.in(free_qpos, n * kPoseWidth);
+  const auto dr = L.out(result, n);
+  const auto dt = L.out(t_contact, n);
+  return staged_call(s, s->d_query, L, [&](auto dev) { return motion_query_dev(s, dev(da), dev(db), dev(df), m, kinds, resolution, dev(dr), dev(dt)); });
 }
 int rcsh_motion_query_dev(rcsh_sim* s, const double* q_from_dev, const double* q_to_dev, const double* free_qpos_dev, int32_t m, int32_t kinds,
                           double resolution, int32_t* result_dev, double* t_contact_dev) {
@@ -1369,28 +1364,17 @@ int clearance_host(rcsh_sim* s, const double* q, const double* free_qpos, int32_
                    double* distance, uint8_t* status, int32_t* pair, double* witness, double* grad, const double* S, int box_field) {
   const size_t nl = (size_t)s->nl, n = (size_t)m;
   const QueryPairs pairs = query_pairs(s, kinds, pair_mask != nullptr);
-  const size_t nmask = pair_mask ? (size_t)pairs.count() : 0;
-  QuerySlices c;
-  const size_t oq = c.take(q ? 8 * n * nl : 0), of = c.take(free_qpos ? 8 * n * 7 : 0), om = c.take(nmask);
-  const size_t od = c.take(8 * n), ow = c.take(8 * n * 6), og = c.take(8 * n * nl), op = c.take(8 * n), os = c.take(n);
-  int rc = grow_device(s, s->d_query, c.total);
-  if (rc) return rc;
-  char* d = static_cast<char*>(s->d_query.p.get());
-  if (q) HIP_TRY(hipMemcpyAsync(d + oq, q, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
-  if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
-  if (nmask) HIP_TRY(hipMemcpyAsync(d + om, pair_mask, nmask, hipMemcpyHostToDevice, s->stream));
-  const ClearOut o{reinterpret_cast<double*>(d + od), reinterpret_cast<uint8_t*>(d + os), reinterpret_cast<int32_t*>(d + op),
-                   reinterpret_cast<double*>(d + ow), reinterpret_cast<double*>(d + og)};
-  rc = clearance_dev(s, pairs, q ? reinterpret_cast<const double*>(d + oq) : nullptr, free_qpos ? reinterpret_cast<const double*>(d + of) : nullptr,
-                     m, kinds, nmask ? reinterpret_cast<const uint8_t*>(d + om) : nullptr, d_max, o, S, box_field);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(distance, o.distance, 8 * n, hipMemcpyDeviceToHost, s->stream));
-  if (status) HIP_TRY(hipMemcpyAsync(status, o.status, n, hipMemcpyDeviceToHost, s->stream));
-  if (pair) HIP_TRY(hipMemcpyAsync(pair, o.pair, 8 * n, hipMemcpyDeviceToHost, s->stream));
-  if (witness) HIP_TRY(hipMemcpyAsync(witness, o.witness, 8 * n * 6, hipMemcpyDeviceToHost, s->stream));
-  if (grad) HIP_TRY(hipMemcpyAsync(grad, o.grad, 8 * n * nl, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return RCSH_OK;
+  StageLayout L;
+  const auto dq = L.in(q, n * nl), df = L.in(free_qpos, n * kPoseWidth);
+  const auto dm = L.in(pair_mask, (size_t)pairs.count());
+  // Unlike the swept and the dynamics form, this one stages all five outputs and hands the kernel all five whatever the caller
+  // asked for; only the ones asked for come back.  Handing it fewer would change the kernel's work.
+  const auto dd = L.out_always(distance, n), dw = L.out_always(witness, n * kWitnessWidth), dg = L.out_always(grad, n * nl);
+  const auto dp = L.out_always(pair, n * kPairWidth);
+  const auto ds = L.out_always(status, n);
+  return staged_call(s, s->d_query, L, [&](auto dev) {
+    return clearance_dev(s, pairs, dev(dq), dev(df), m, kinds, dev(dm), d_max, ClearOut{dev(dd), dev(ds), dev(dp), dev(dw), dev(dg)}, S, box_field);
+  });
 }
 // the free body of the environments' own rows: tested when the scene has one and `kinds` asks for it
 int env_clearance_box_field(rcsh_sim* s, int32_t kinds) { return (kinds & kQueryBox) && s->box.present ? field_of(s, "box") + kBoxQ : -1; }
@@ -1414,7 +1398,7 @@ int rcsh_clearance_query(rcsh_sim* s, const double* q, const double* free_qpos, 
   if (m == 0) return RCSH_OK;
   if (!q || !distance) return fail(RCSH_ERR_ARG, "null argument");
   if ((rc = query_finite(q, (size_t)m * s->nl, "q"))) return rc;
-  if (free_qpos && (rc = query_finite(free_qpos, (size_t)m * 7, "free_qpos"))) return rc;
+  if (free_qpos && (rc = query_finite(free_qpos, (size_t)m * kPoseWidth, "free_qpos"))) return rc;
   return clearance_host(s, q, free_qpos, m, kinds, pair_mask, d_max, distance, status, pair, witness, grad, nullptr, -1);
 }
 int rcsh_clearance_query_dev(rcsh_sim* s, const double* q_dev, const double* free_qpos_dev, int32_t m, int32_t kinds, const uint8_t* pair_mask_dev,
@@ -1481,32 +1465,20 @@ int swept_host(rcsh_sim* s, const double* q_from, const double* q_to, const doub
                double d_max, double tolerance, double resolution, const rcsh_swept_out& o, const double* S, int box_field) {
   const size_t nl = (size_t)s->nl, n = (size_t)m;
   const QueryPairs pairs = query_pairs(s, kinds, pair_mask != nullptr);
-  const size_t nmask = pair_mask ? (size_t)pairs.count() : 0;
-  void* const host[8] = {o.distance, o.lower, o.s, o.pair, o.witness, o.grad, o.evals, o.status};
-  const size_t bytes[8] = {8 * n, 8 * n, 8 * n, 8 * n, 8 * n * 6, 8 * n * nl, 4 * n, n};
-  QuerySlices c;
-  const size_t oa = c.take(q_from ? 8 * n * nl : 0), ob = c.take(8 * n * nl), of = c.take(free_qpos ? 8 * n * 7 : 0), om = c.take(nmask);
-  size_t oo[8];
-  for (int k = 0; k < 8; ++k) oo[k] = c.take(host[k] ? bytes[k] : 0);
-  int rc = grow_device(s, s->d_query, c.total);
-  if (rc) return rc;
-  char* d = static_cast<char*>(s->d_query.p.get());
-  if (q_from) HIP_TRY(hipMemcpyAsync(d + oa, q_from, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(d + ob, q_to, 8 * n * nl, hipMemcpyHostToDevice, s->stream));
-  if (free_qpos) HIP_TRY(hipMemcpyAsync(d + of, free_qpos, 8 * n * 7, hipMemcpyHostToDevice, s->stream));
-  if (nmask) HIP_TRY(hipMemcpyAsync(d + om, pair_mask, nmask, hipMemcpyHostToDevice, s->stream));
-  void* dev[8];
-  for (int k = 0; k < 8; ++k) dev[k] = host[k] ? d + oo[k] : nullptr;
-  const rcsh_swept_out od{static_cast<double*>(dev[0]), static_cast<double*>(dev[1]), static_cast<double*>(dev[2]), static_cast<int32_t*>(dev[3]),
-                          static_cast<double*>(dev[4]), static_cast<double*>(dev[5]), static_cast<int32_t*>(dev[6]), static_cast<uint8_t*>(dev[7])};
-  rc = swept_dev(s, pairs, q_from ? reinterpret_cast<const double*>(d + oa) : nullptr, reinterpret_cast<const double*>(d + ob),
-                 free_qpos ? reinterpret_cast<const double*>(d + of) : nullptr, m, kinds, nmask ? reinterpret_cast<const uint8_t*>(d + om) : nullptr,
-                 d_max, tolerance, resolution, od, S, box_field);
-  if (rc) return rc;
-  for (int k = 0; k < 8; ++k)
-    if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return RCSH_OK;
+  StageLayout L;
+  const auto da = L.in(q_from, n * nl), db = L.in(q_to, n * nl), df = L.in(free_qpos, n * kPoseWidth);
+  const auto dm = L.in(pair_mask, (size_t)pairs.count());
+  const auto dd = L.out(o.distance, n), dl = L.out(o.lower, n), dx = L.out(o.s, n);
+  const auto dp = L.out(o.pair, n * kPairWidth);
+  const auto dw = L.out(o.witness, n * kWitnessWidth), dg = L.out(o.grad, n * nl);
+  const auto de = L.out(o.evals, n);
+  const auto du = L.out(o.status, n);
+  return staged_call(s, s->d_query, L, [&](auto dev) {
+    rcsh_swept_out od{};
+    od.distance = dev(dd); od.lower = dev(dl); od.s = dev(dx); od.pair = dev(dp);
+    od.witness = dev(dw); od.grad = dev(dg); od.evals = dev(de); od.status = dev(du);
+    return swept_dev(s, pairs, dev(da), dev(db), dev(df), m, kinds, dev(dm), d_max, tolerance, resolution, od, S, box_field);
+  });
 }
 }  // namespace
 
@@ -1518,7 +1490,7 @@ int rcsh_swept_clearance(rcsh_sim* s, const double* q_from, const double* q_to, 
   if (m == 0) return RCSH_OK;
   if (!q_from || !q_to || !out || !out->distance) return fail(RCSH_ERR_ARG, "null argument");
   if ((rc = query_finite(q_from, (size_t)m * s->nl, "q_from")) || (rc = query_finite(q_to, (size_t)m * s->nl, "q_to"))) return rc;
-  if (free_qpos && (rc = query_finite(free_qpos, (size_t)m * 7, "free_qpos"))) return rc;
+  if (free_qpos && (rc = query_finite(free_qpos, (size_t)m * kPoseWidth, "free_qpos"))) return rc;
   return swept_host(s, q_from, q_to, free_qpos, m, kinds, pair_mask, d_max, tolerance, resolution, *out, nullptr, -1);
 }
 int rcsh_swept_clearance_dev(rcsh_sim* s, const double* q_from_dev, const double* q_to_dev, const double* free_qpos_dev, int32_t m, int32_t kinds,
@@ -1594,34 +1566,22 @@ int dynamics_dev(rcsh_sim* s, const double* q, const double* qvel, const double*
 // the host form of both queries: q null: the environments' own rows
 int dynamics_host(rcsh_sim* s, const double* q, const double* qvel, const double* qacc_in, const double* qfrc_in, int32_t m, const double* tcp_p,
                   const rcsh_dynamics_out& o, const double* S) {
-  const size_t nl = (size_t)s->nl, n = (size_t)m, row = 8 * n * nl;
+  const size_t nl = (size_t)s->nl, n = (size_t)m, row = n * nl;
   const double* in[4] = {q, qvel, o.qfrc_inverse ? qacc_in : nullptr, o.qacc ? qfrc_in : nullptr};
   const char* names[4] = {"q", "qvel", "qacc_in", "qfrc_in"};
   for (int k = 0; k < 4; ++k)
     if (in[k])
       if (int rc = query_finite(in[k], n * nl, names[k])) return rc;
-  double* const host[7] = {o.qM, o.qfrc_bias, o.gravity, o.qfrc_gravcomp, o.jac, o.qfrc_inverse, o.qacc};
-  const size_t bytes[7] = {row * nl, row, row, row, row * 6, row, row};
-  QuerySlices c;
-  size_t oi[4], oo[7];
-  for (int k = 0; k < 4; ++k) oi[k] = c.take(in[k] ? row : 0);
-  for (int k = 0; k < 7; ++k) oo[k] = c.take(host[k] ? bytes[k] : 0);
-  int rc = grow_device(s, s->d_query, c.total);
-  if (rc) return rc;
-  char* d = static_cast<char*>(s->d_query.p.get());
-  const double* din[4];
-  for (int k = 0; k < 4; ++k) {
-    din[k] = in[k] ? reinterpret_cast<const double*>(d + oi[k]) : nullptr;
-    if (in[k]) HIP_TRY(hipMemcpyAsync(d + oi[k], in[k], row, hipMemcpyHostToDevice, s->stream));
-  }
-  double* dout[7];
-  for (int k = 0; k < 7; ++k) dout[k] = host[k] ? reinterpret_cast<double*>(d + oo[k]) : nullptr;
-  const rcsh_dynamics_out od{dout[0], dout[1], dout[2], dout[3], dout[4], dout[5], dout[6]};
-  if ((rc = dynamics_dev(s, din[0], din[1], din[2], din[3], m, tcp_p, od, S))) return rc;
-  for (int k = 0; k < 7; ++k)
-    if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], dout[k], bytes[k], hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return RCSH_OK;
+  StageLayout L;
+  const auto dq = L.in(in[0], row), dv = L.in(in[1], row), da = L.in(in[2], row), df = L.in(in[3], row);
+  const auto dM = L.out(o.qM, row * nl), db = L.out(o.qfrc_bias, row), dg = L.out(o.gravity, row), dc = L.out(o.qfrc_gravcomp, row);
+  const auto dj = L.out(o.jac, row * kJacRows), di = L.out(o.qfrc_inverse, row), dx = L.out(o.qacc, row);
+  return staged_call(s, s->d_query, L, [&](auto dev) {
+    rcsh_dynamics_out od{};
+    od.qM = dev(dM); od.qfrc_bias = dev(db); od.gravity = dev(dg); od.qfrc_gravcomp = dev(dc);
+    od.jac = dev(dj); od.qfrc_inverse = dev(di); od.qacc = dev(dx);
+    return dynamics_dev(s, dev(dq), dev(dv), dev(da), dev(df), m, tcp_p, od, S);
+  });
 }
 }  // namespace
 
@@ -2228,6 +2188,12 @@ GuardRecord guard_record(const rcsh_sim* s, int which) {  // 0: the last guarded
   r.hold = reinterpret_cast<uint8_t*>(d + G.hold);
   return r;
 }
+// a host form's downloads of a record's arrays, read where they lie (null: not asked for)
+void guard_outputs(StageLayout& L, const GuardRecord& r, size_t n, int32_t* result, double* t_contact, uint8_t* blocked) {
+  L.out_from(result, r.result, n);
+  L.out_from(t_contact, r.t_contact, n);
+  L.out_from(blocked, r.blocked, n);
+}
 __global__ void k_guard_fill(int32_t* result, double* t_contact, uint8_t* blocked, uint8_t* hold, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) { result[i] = 0; t_contact[i] = -1.0; blocked[i] = 0; if (hold) hold[i] = kGuardLive; }
@@ -2313,16 +2279,11 @@ int rcsh_env_guard_peek(rcsh_sim* s, const double* action, int32_t* result, doub
   const size_t n = (size_t)s->n, na = n * (size_t)s->narm;
   int rc = query_finite(action, na, "action");
   if (rc) return rc;
-  if ((rc = grow_device(s, s->d_query, 8 * na))) return rc;
-  double* d_action = static_cast<double*>(s->d_query.p.get());
-  const GuardRecord r = guard_record(s, 1);
-  HIP_TRY(hipMemcpyAsync(d_action, action, 8 * na, hipMemcpyHostToDevice, s->stream));
-  if ((rc = guard_launch(s, d_action, r.result, r.t_contact, r.blocked, nullptr))) return rc;
-  if (result) HIP_TRY(hipMemcpyAsync(result, r.result, 4 * n, hipMemcpyDeviceToHost, s->stream));
-  if (t_contact) HIP_TRY(hipMemcpyAsync(t_contact, r.t_contact, 8 * n, hipMemcpyDeviceToHost, s->stream));
-  if (blocked) HIP_TRY(hipMemcpyAsync(blocked, r.blocked, n, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return RCSH_OK;
+  const GuardRecord r = guard_record(s, 1);  // (the answers land in the guard's scratch record, not in the staging)
+  StageLayout L;
+  const auto da = L.in(action, na);
+  guard_outputs(L, r, n, result, t_contact, blocked);
+  return staged_call(s, s->d_query, L, [&](auto dev) { return guard_launch(s, dev(da), r.result, r.t_contact, r.blocked, nullptr); });
 }
 
 int rcsh_env_guard_last_dev(rcsh_sim* s, const int32_t** result_dev, const double** t_contact_dev, const uint8_t** blocked_dev) {
@@ -2347,12 +2308,9 @@ int rcsh_env_guard_last(rcsh_sim* s, int32_t* result, double* t_contact, uint8_t
     if (blocked) std::memcpy(blocked, hg + G.blocked, n);
     return RCSH_OK;
   }
-  const GuardRecord r = guard_record(s, 0);
-  if (result) HIP_TRY(hipMemcpyAsync(result, r.result, 4 * n, hipMemcpyDeviceToHost, s->stream));
-  if (t_contact) HIP_TRY(hipMemcpyAsync(t_contact, r.t_contact, 8 * n, hipMemcpyDeviceToHost, s->stream));
-  if (blocked) HIP_TRY(hipMemcpyAsync(blocked, r.blocked, n, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return RCSH_OK;
+  StageLayout L;  // (nothing staged: the record is read where it lies)
+  guard_outputs(L, guard_record(s, 0), n, result, t_contact, blocked);
+  return staged_call(s, s->d_query, L, [](auto) { return (int)RCSH_OK; });
 }
 
 int rcsh_env_step_dev(rcsh_sim* s, const double* action_dev, const float* gripper_dev, double* obs_dev, uint8_t* info_dev,
@@ -2814,24 +2772,13 @@ int rcsh_camera_render_dev(rcsh_sim* s, int32_t cam_id, float* depth_gl, uint16_
 int rcsh_camera_render_rgb(rcsh_sim* s, int32_t cam_id, uint8_t* rgb, float* depth_gl, uint16_t* depth_mm, double* cam_pose) {
   REQUIRE_SIM(s);
   if (cam_id < 0 || cam_id >= (int)s->cams.size()) return fail(RCSH_ERR_ARG, "unknown camera id");
-  const size_t px = (size_t)s->n * s->cams[cam_id].width * s->cams[cam_id].height;
-  // device staging: f32 depth, u16 depth, camera poses (8-byte aligned), rgb
-  const size_t off_mm = px * sizeof(float), off_pose = ((off_mm + px * sizeof(uint16_t) + 7) / 8) * 8, off_rgb = off_pose + sizeof(double) * 12 * s->n;
-  const size_t need = off_rgb + 3 * px;
-  if (int rc = grow_device(s, s->d_image, need)) return rc;
-  char* base = static_cast<char*>(s->d_image.p.get());
-  float* dgl = reinterpret_cast<float*>(base);
-  uint16_t* dmm = reinterpret_cast<uint16_t*>(base + off_mm);
-  double* dpose = reinterpret_cast<double*>(base + off_pose);
-  uint8_t* drgb = reinterpret_cast<uint8_t*>(base + off_rgb);
-  int rc = rcsh_camera_render_rgb_dev(s, cam_id, rgb ? drgb : nullptr, depth_gl ? dgl : nullptr, depth_mm ? dmm : nullptr, cam_pose ? dpose : nullptr);
-  if (rc) return rc;
-  if (rgb) HIP_TRY(hipMemcpyAsync(rgb, drgb, 3 * px, hipMemcpyDeviceToHost, s->stream));
-  if (depth_gl) HIP_TRY(hipMemcpyAsync(depth_gl, dgl, px * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-  if (depth_mm) HIP_TRY(hipMemcpyAsync(depth_mm, dmm, px * sizeof(uint16_t), hipMemcpyDeviceToHost, s->stream));
-  if (cam_pose) HIP_TRY(hipMemcpyAsync(cam_pose, dpose, sizeof(double) * 12 * s->n, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return RCSH_OK;
+  const size_t n = (size_t)s->n, px = n * s->cams[cam_id].width * s->cams[cam_id].height;
+  StageLayout L;
+  const auto dgl = L.out(depth_gl, px);
+  const auto dmm = L.out(depth_mm, px);
+  const auto dpose = L.out(cam_pose, n * kCamPoseWidth);
+  const auto drgb = L.out(rgb, px * kRgbWidth);
+  return staged_call(s, s->d_image, L, [&](auto dev) { return rcsh_camera_render_rgb_dev(s, cam_id, dev(drgb), dev(dgl), dev(dmm), dev(dpose)); });
 }
 
 int rcsh_camera_render(rcsh_sim* s, int32_t cam_id, float* depth_gl, uint16_t* depth_mm, double* cam_pose) {

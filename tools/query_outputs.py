@@ -1,5 +1,5 @@
-"""dev tool (GPU): every output array of the query family -- point, motion, clearance, env clearance, guard peek -- from seeded inputs,
-for comparing two builds of the library bit for bit (RCSH_LIB selects the build).
+"""dev tool (GPU): every output array of the query family -- point, motion, clearance, swept clearance, dynamics, their env forms, guard
+peek -- through the host-pointer forms from seeded inputs, for comparing two builds of the library bit for bit (RCSH_LIB selects the build).
 
     RCSH_LIB=<lib.so> python tools/query_outputs.py OUT_DIR          one .npy per array
     python tools/query_outputs.py --compare DIR_A DIR_B              array_equal on every array; exit 1 on a difference
@@ -86,6 +86,9 @@ def dump(out):
             np.save(os.path.join(out, f"{tag}_{n}.npy"), np.asarray(a))
 
     clear_names = ("distance", "status", "pair", "witness", "grad")
+
+    def save_dict(tag, arrays):
+        save(tag, sorted(arrays), [arrays[k] for k in sorted(arrays)])
     for name in ("fr3_empty_world", "fr3_simple_pick_up", "xarm7_pick_world"):
         for m in (M_SMALL, M_LARGE):
             robot, q, q_to, boxes, kinds = rows_for(name, m)
@@ -99,6 +102,15 @@ def dump(out):
                 res = robot.check_clearance(q, free_qpos=boxes, kinds=kinds, **kw)
                 save(f"{tag}_clearance_{ctag}", clear_names, res)
                 print(tag, ctag, "status apart/beyond/contact/open", np.bincount(res[1], minlength=4).tolist(), flush=True)
+            # swept clearance (1 cm brackets and samples: the large batch stays a matter of seconds) and dynamics, every output and a few
+            for stag, kw in (("all", {}), ("masked_dmax005_no_grad", {"pair_mask": mask, "d_max": 0.05, "want_grad": False})):
+                res = robot.swept_clearance(q, q_to, tolerance=1e-2, resolution=1e-2, free_qpos=boxes, kinds=kinds, **kw)
+                save_dict(f"{tag}_swept_{stag}", res)
+                print(tag, "swept", stag, "status bracketed/beyond/contact/open", np.bincount(res["status"], minlength=4).tolist(), flush=True)
+            rng = np.random.default_rng(40 + m)
+            v, a, f = (rng.uniform(-1, 1, q.shape) for _ in range(3))
+            save_dict(f"{tag}_dynamics_all", robot.dynamics_query(q, v, a, f, tcp_offset=None))
+            save_dict(f"{tag}_dynamics_jac_inverse", robot.dynamics_query(q, v, qacc=a, want=("jac", "qfrc_inverse")))
     # the env forms: the environments' own rows after three steps
     from parity_util import make_vec_env, synthetic_actions
     from test_gpu_clearance import _pick_env
@@ -112,6 +124,13 @@ def dump(out):
         mask[::3] = 0
         for ctag, kw in (("inf", {}), ("dmax005", {"d_max": 0.05}), ("masked", {"pair_mask": mask})):
             save(f"{tag}_clearance_{ctag}", clear_names, venv.clearance(kinds=kinds, **kw))
+        nl = int(venv.sim.model.nq)
+        q_to = venv.sim.qpos[:, :nl] + np.random.default_rng(50).uniform(-0.2, 0.2, (N_ENVS, nl)) * np.array([1.0] * venv.robot.dof + [0.0] * (nl - venv.robot.dof))
+        save_dict(f"{tag}_swept_all", venv.swept_clearance(q_to, tolerance=1e-2, resolution=1e-2, kinds=kinds))
+        save_dict(f"{tag}_swept_masked_dmax005", venv.swept_clearance(q_to, tolerance=1e-2, resolution=1e-2, kinds=kinds, pair_mask=mask, d_max=0.05))
+        f = np.random.default_rng(51).uniform(-1, 1, (N_ENVS, nl))
+        save_dict(f"{tag}_dynamics_all", venv.dynamics(qacc=f[::-1], qfrc=f))
+        save_dict(f"{tag}_dynamics_bias_gravity", venv.dynamics(want=("qfrc_bias", "gravity")))
         venv.configure_guard(enabled=False, kinds=kinds)
         for scale in (1.0, 8.0):  # (the second: actions large enough to be clamped, some into contact)
             save(f"{tag}_guard_x{scale:g}", ("blocked", "result", "t_contact"), venv.check_action({"joints": scale * joints[3]}))
