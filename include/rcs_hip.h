@@ -410,6 +410,38 @@ int rcsh_env_dynamics(rcsh_sim* sim, const double* qacc_in, const double* qfrc_i
 int rcsh_env_dynamics_dev(rcsh_sim* sim, const double* qacc_in_dev, const double* qfrc_in_dev, const double* tcp_offset7,
                           const rcsh_dynamics_out* out_dev);
 
+/* ---- dynamics derivatives: how qfrc_inverse and qacc of the dynamics queries change with the state (csrc/dynamics_grad_team.h).
+ * What iLQR / DDP, SQP-style MPC and linearised feedback need of the chain, analytically (the differentiated recursive Newton-Euler
+ * pass; no finite difference on the device), for M rows at once.  Rows q, qvel (NULL: zero), qacc_in, qfrc_in are [M][nl] as in
+ * rcsh_dynamics_query; like it the call reads and writes NO per-environment state and runs on the handle's stream.
+ * Every output is [M][nl][nl] row-major, element [i][k] the derivative of component i by variable k; every pointer of
+ * rcsh_dynamics_grad_out may be NULL (not wanted), and an output's bits do not depend on which others are asked for:
+ *   dqfrc_inverse_dq     d(M(q) qacc_in + qfrc_bias(q, qvel)) / dq at the row's (q, qvel, qacc_in);
+ *   dqfrc_inverse_dqvel  d qfrc_bias / d qvel (does not depend on qacc_in);
+ *   dqacc_dq             d(M^-1 (qfrc_in - qfrc_bias)) / dq = -M^-1 d(qfrc_inverse)/dq taken at the row's own qacc;
+ *   dqacc_dqvel          -M^-1 d qfrc_bias / d qvel;
+ *   qM_inv               M^-1, full symmetric: d qacc / d qfrc_in.
+ * They differentiate exactly what rcsh_dynamics_query returns: armature is part of M, the finger slides are part of the chain, and no
+ * actuator, damping, gravity-compensation, limit, equality, friction or contact term enters.
+ * RCSH_ERR_STATE: no robot attached.  RCSH_ERR_ARG: M < 0; a null q or a null `out` where M > 0; dqfrc_inverse_dq asked for without
+ * qacc_in; dqacc_dq or dqacc_dqvel without qfrc_in; a non-finite input entry (host forms only).  M = 0 does nothing.
+ * rcsh_env_dynamics_derivatives asks the same once per environment (M = n_envs) at the environment's own chain qpos and qvel;
+ * qacc_in and qfrc_in are [N][nl].  It writes nothing but its outputs. */
+typedef struct rcsh_dynamics_grad_out {
+  double* dqfrc_inverse_dq;     /* [M][nl][nl]; needs qacc_in */
+  double* dqfrc_inverse_dqvel;  /* [M][nl][nl] */
+  double* dqacc_dq;             /* [M][nl][nl]; needs qfrc_in */
+  double* dqacc_dqvel;          /* [M][nl][nl]; needs qfrc_in */
+  double* qM_inv;               /* [M][nl][nl] */
+} rcsh_dynamics_grad_out;
+int rcsh_dynamics_derivatives(rcsh_sim* sim, const double* q, const double* qvel, const double* qacc_in, const double* qfrc_in,
+                              int32_t m, const rcsh_dynamics_grad_out* out);
+int rcsh_dynamics_derivatives_dev(rcsh_sim* sim, const double* q_dev, const double* qvel_dev, const double* qacc_in_dev,
+                                  const double* qfrc_in_dev, int32_t m, const rcsh_dynamics_grad_out* out_dev);
+int rcsh_env_dynamics_derivatives(rcsh_sim* sim, const double* qacc_in, const double* qfrc_in, const rcsh_dynamics_grad_out* out);
+int rcsh_env_dynamics_derivatives_dev(rcsh_sim* sim, const double* qacc_in_dev, const double* qfrc_in_dev,
+                                      const rcsh_dynamics_grad_out* out_dev);
+
 /* SimGripper(sim, cfg) -- rcs.cpp:508-515, SimGripper.cpp:13-39 */
 int rcsh_sim_add_gripper(rcsh_sim* sim, const rcsh_gripper_desc* gripper);
 /* Gripper.set_normalized_width -- rcs.cpp:383-384, SimGripper.cpp:79-92 (RCSH_ERR_ARG outside [0,1] / force<0) */

@@ -25,6 +25,7 @@
 #include "clearance_team.h"
 #include "swept_team.h"
 #include "dynamics_team.h"
+#include "dynamics_grad_team.h"
 #include "guard_team.h"
 #include "episode_team.h"
 
@@ -1619,6 +1620,79 @@ int rcsh_env_dynamics_dev(rcsh_sim* s, const double* qacc_in_dev, const double* 
   int rc = dynamics_check(s, s->n, qacc_in_dev, qfrc_in_dev, tcp_offset7, out_dev, tcp_p);
   if (rc) return rc;
   return dynamics_dev(s, nullptr, nullptr, qacc_in_dev, qfrc_in_dev, s->n, tcp_p, *out_dev, s->S.get());
+}
+
+// ---- dynamics derivatives (csrc/dynamics_grad_team.h)
+namespace {
+// what every form checks before anything is read
+int dynamics_grad_check(int32_t m, const double* qacc_in, const double* qfrc_in, const rcsh_dynamics_grad_out* out) {
+  if (m < 0) return fail(RCSH_ERR_ARG, "negative query count");
+  if (m > 0 && !out) return fail(RCSH_ERR_ARG, "null argument");
+  if (out && out->dqfrc_inverse_dq && !qacc_in) return fail(RCSH_ERR_ARG, "dqfrc_inverse_dq asked for without qacc_in");
+  if (out && (out->dqacc_dq || out->dqacc_dqvel) && !qfrc_in) return fail(RCSH_ERR_ARG, "dqacc_dq / dqacc_dqvel asked for without qfrc_in");
+  return RCSH_OK;
+}
+// device pointers in; S non-null: the environments' own rows (m = n_envs)
+int dynamics_grad_dev(rcsh_sim* s, const double* q, const double* qvel, const double* qacc_in, const double* qfrc_in, int32_t m,
+                      const rcsh_dynamics_grad_out& o, const double* S) {
+  DynGradArgs A{};
+  A.links = reinterpret_cast<const LinkRec*>(reinterpret_cast<const char*>(s->d_model.get()) + sizeof(DevModel));
+  A.m = m;
+  for (int k = 0; k < 3; ++k) A.gravity[k] = s->dm.gravity[k];
+  A.q = q; A.qvel = qvel; A.qacc_in = qacc_in; A.qfrc_in = qfrc_in;
+  A.o = DynGradOut{o.dqfrc_inverse_dq, o.dqfrc_inverse_dqvel, o.dqacc_dq, o.dqacc_dqvel, o.qM_inv};
+  A.S = S; A.qpos_field = field_of(s, "qpos"); A.qvel_field = field_of(s, "qvel");
+  return team_launch(s, m, "dynamics derivatives", [&](auto topo, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(k_dynamics_derivatives<decltype(topo)>, grid, block, 0, s->stream, A);
+  });
+}
+// the host form of both: q null: the environments' own rows
+int dynamics_grad_host(rcsh_sim* s, const double* q, const double* qvel, const double* qacc_in, const double* qfrc_in, int32_t m,
+                       const rcsh_dynamics_grad_out& o, const double* S) {
+  const size_t nl = (size_t)s->nl, n = (size_t)m, row = n * nl, mat = row * nl;
+  const double* in[4] = {q, qvel, o.dqfrc_inverse_dq ? qacc_in : nullptr, o.dqacc_dq ? qfrc_in : nullptr};
+  const char* names[4] = {"q", "qvel", "qacc_in", "qfrc_in"};
+  for (int k = 0; k < 4; ++k)
+    if (in[k])
+      if (int rc = query_finite(in[k], row, names[k])) return rc;
+  StageLayout L;
+  const auto dq = L.in(in[0], row), dv = L.in(in[1], row), da = L.in(in[2], row), df = L.in(in[3], row);
+  const auto d0 = L.out(o.dqfrc_inverse_dq, mat), d1 = L.out(o.dqfrc_inverse_dqvel, mat), d2 = L.out(o.dqacc_dq, mat);
+  const auto d3 = L.out(o.dqacc_dqvel, mat), d4 = L.out(o.qM_inv, mat);
+  return staged_call(s, s->d_query, L, [&](auto dev) {
+    rcsh_dynamics_grad_out od{};
+    od.dqfrc_inverse_dq = dev(d0); od.dqfrc_inverse_dqvel = dev(d1); od.dqacc_dq = dev(d2); od.dqacc_dqvel = dev(d3); od.qM_inv = dev(d4);
+    return dynamics_grad_dev(s, dev(dq), dev(dv), dev(da), dev(df), m, od, S);
+  });
+}
+}  // namespace
+
+int rcsh_dynamics_derivatives(rcsh_sim* s, const double* q, const double* qvel, const double* qacc_in, const double* qfrc_in, int32_t m,
+                              const rcsh_dynamics_grad_out* out) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (int rc = dynamics_grad_check(m, qacc_in, qfrc_in, out)) return rc;
+  if (m == 0) return RCSH_OK;
+  if (!q) return fail(RCSH_ERR_ARG, "null argument");
+  return dynamics_grad_host(s, q, qvel, qacc_in, qfrc_in, m, *out, nullptr);
+}
+int rcsh_dynamics_derivatives_dev(rcsh_sim* s, const double* q_dev, const double* qvel_dev, const double* qacc_in_dev,
+                                  const double* qfrc_in_dev, int32_t m, const rcsh_dynamics_grad_out* out_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (int rc = dynamics_grad_check(m, qacc_in_dev, qfrc_in_dev, out_dev)) return rc;
+  if (m == 0) return RCSH_OK;
+  if (!q_dev) return fail(RCSH_ERR_ARG, "null argument");
+  return dynamics_grad_dev(s, q_dev, qvel_dev, qacc_in_dev, qfrc_in_dev, m, *out_dev, nullptr);
+}
+int rcsh_env_dynamics_derivatives(rcsh_sim* s, const double* qacc_in, const double* qfrc_in, const rcsh_dynamics_grad_out* out) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (int rc = dynamics_grad_check(s->n, qacc_in, qfrc_in, out)) return rc;
+  return dynamics_grad_host(s, nullptr, nullptr, qacc_in, qfrc_in, s->n, *out, s->S.get());
+}
+int rcsh_env_dynamics_derivatives_dev(rcsh_sim* s, const double* qacc_in_dev, const double* qfrc_in_dev,
+                                      const rcsh_dynamics_grad_out* out_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (int rc = dynamics_grad_check(s->n, qacc_in_dev, qfrc_in_dev, out_dev)) return rc;
+  return dynamics_grad_dev(s, nullptr, nullptr, qacc_in_dev, qfrc_in_dev, s->n, *out_dev, s->S.get());
 }
 
 int rcsh_robot_get_state(rcsh_sim* s, uint8_t* ik_success, uint8_t* collision, uint8_t* is_moving, uint8_t* is_arrived,

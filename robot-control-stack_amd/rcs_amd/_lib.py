@@ -178,6 +178,12 @@ class DynamicsOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("qM", "qfrc_bias", "gravity", "qfrc_gravcomp", "jac", "qfrc_inverse", "qacc")]
 
 
+class DynamicsGradOut(C.Structure):
+    """Output pointers of the dynamics derivatives (rcsh_dynamics_grad_out), each [M][nl][nl]: host arrays, or device addresses for the
+    _dev forms; NULL: not wanted."""
+    _fields_ = [(name, C.c_void_p) for name in ("dqfrc_inverse_dq", "dqfrc_inverse_dqvel", "dqacc_dq", "dqacc_dqvel", "qM_inv")]
+
+
 class SweptOut(C.Structure):
     """Output pointers of the swept clearance queries (rcsh_swept_out): host arrays, or device addresses for the _dev forms; NULL: not
     wanted (``distance`` is required)."""
@@ -216,6 +222,7 @@ EXPORTS = (
     "rcsh_clearance_pairs", "rcsh_clearance_query", "rcsh_clearance_query_dev", "rcsh_env_clearance", "rcsh_env_clearance_dev",
     "rcsh_swept_clearance", "rcsh_swept_clearance_dev", "rcsh_env_swept_clearance", "rcsh_env_swept_clearance_dev",
     "rcsh_dynamics_query", "rcsh_dynamics_query_dev", "rcsh_env_dynamics", "rcsh_env_dynamics_dev",
+    "rcsh_dynamics_derivatives", "rcsh_dynamics_derivatives_dev", "rcsh_env_dynamics_derivatives", "rcsh_env_dynamics_derivatives_dev",
     "rcsh_env_configure_guard", "rcsh_env_guard_peek", "rcsh_env_guard_peek_dev", "rcsh_env_guard_last", "rcsh_env_guard_last_dev",
     "rcsh_env_configure_autoreset", "rcsh_env_autoreset_record_dev", "rcsh_env_autoreset_last", "rcsh_autoreset_draw",
 )
@@ -312,6 +319,10 @@ def load() -> C.CDLL:
         fn.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.POINTER(DynamicsOut)]
     for fn in (L.rcsh_env_dynamics, L.rcsh_env_dynamics_dev):
         fn.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.POINTER(DynamicsOut)]
+    for fn in (L.rcsh_dynamics_derivatives, L.rcsh_dynamics_derivatives_dev):
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32, C.POINTER(DynamicsGradOut)]
+    for fn in (L.rcsh_env_dynamics_derivatives, L.rcsh_env_dynamics_derivatives_dev):
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 2 + [C.POINTER(DynamicsGradOut)]
     L.rcsh_env_configure_guard.argtypes = [C.c_void_p, C.POINTER(GuardDesc)]
     for fn in (L.rcsh_env_guard_peek, L.rcsh_env_guard_peek_dev):
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

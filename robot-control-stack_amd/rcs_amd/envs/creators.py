@@ -237,6 +237,18 @@ class VecSimEnv:
         _lib.check(self._L.rcsh_env_dynamics(self.sim._h, _lib.ptr(a), _lib.ptr(f), _lib.ptr(tcp), C.byref(out)))
         return arrays
 
+    def dynamics_derivatives(self, want=None, qacc=None, qfrc=None) -> dict:
+        """Every environment's dynamics linearised where it is now: the Jacobians of ``qfrc_inverse`` and ``qacc`` at its own chain
+        ``qpos`` and ``qvel``.  ``want``, ``qacc`` / ``qfrc`` ([N, nl]) and the returned dict of arrays [N, nl, nl] as
+        :meth:`rcs_amd.sim.SimRobot.dynamics_derivatives`.  Reads the state, writes none of it."""
+        n, nl = self.n_envs, int(self.sim.model.nq)
+        want = self.robot._dynamics_grad_want(want, qacc, qfrc)
+        rows = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (n, nl)))  # noqa: E731
+        a, f = rows(qacc), rows(qfrc)
+        arrays, out = self.robot._dynamics_grad_buffers(want, n, nl)
+        _lib.check(self._L.rcsh_env_dynamics_derivatives(self.sim._h, _lib.ptr(a), _lib.ptr(f), C.byref(out)))
+        return arrays
+
     def _guard_info(self, i: dict[str, Any]):
         """info["guard_*"] of a guarded step; returns ``blocked`` where it truncates (else None)."""
         if not self.guard_enabled:

@@ -714,6 +714,42 @@ class SimRobot:
         _lib.check(self._L.rcsh_dynamics_query(self.sim._h, _lib.ptr(rows), _lib.ptr(v), _lib.ptr(a), _lib.ptr(f), m, _lib.ptr(tcp), C.byref(out)))
         return arrays
 
+    # outputs of the dynamics derivatives, in the order of rcsh_dynamics_grad_out; each [M, nl, nl]
+    DYNAMICS_DERIVATIVES = ("dqfrc_inverse_dq", "dqfrc_inverse_dqvel", "dqacc_dq", "dqacc_dqvel", "qM_inv")
+
+    def _dynamics_grad_want(self, want, qacc, qfrc) -> tuple:
+        if want is None:
+            want = tuple(k for k in self.DYNAMICS_DERIVATIVES
+                         if (k != "dqfrc_inverse_dq" or qacc is not None) and (k not in ("dqacc_dq", "dqacc_dqvel") or qfrc is not None))
+        want = (want,) if isinstance(want, str) else tuple(want)
+        unknown = [k for k in want if k not in self.DYNAMICS_DERIVATIVES]
+        if unknown:
+            raise ValueError(f"unknown dynamics derivative {unknown}: one of {self.DYNAMICS_DERIVATIVES}")
+        return want
+
+    def _dynamics_grad_buffers(self, want, m: int, nl: int):
+        arrays = {k: np.zeros((m, nl, nl)) for k in want}
+        return arrays, _lib.DynamicsGradOut(**{k: a.ctypes.data for k, a in arrays.items()})
+
+    def dynamics_derivatives(self, q, qvel=None, qacc=None, qfrc=None, want=None, finger_qpos=None) -> dict:
+        """Analytic Jacobians of what :meth:`dynamics_query` returns as ``qfrc_inverse`` and ``qacc``, for M caller-supplied states at
+        once, without touching any environment's state.
+
+        q, qvel, qacc, qfrc: as in :meth:`dynamics_query`.  ``want``: names out of ``DYNAMICS_DERIVATIVES`` (None: every output its
+        inputs allow).  Returns a dict of arrays [M, nl, nl], element [i, k] the derivative of component i by variable k:
+        ``dqfrc_inverse_dq`` = d(M qacc + qfrc_bias)/dq (needs ``qacc``), ``dqfrc_inverse_dqvel`` = d qfrc_bias/d qvel, ``dqacc_dq`` and
+        ``dqacc_dqvel`` = the derivatives of M^-1 (qfrc - qfrc_bias) (need ``qfrc``), ``qM_inv`` = M^-1 = d qacc/d qfrc
+        (include/rcs_hip.h, rcsh_dynamics_derivatives)."""
+        rows = self._query_rows(q, finger_qpos, "q")
+        m, nl = rows.shape
+        want = self._dynamics_grad_want(want, qacc, qfrc)
+
+        like = lambda x: None if x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (m, nl)))  # noqa: E731
+        v, a, f = like(qvel), like(qacc), like(qfrc)
+        arrays, out = self._dynamics_grad_buffers(want, m, nl)
+        _lib.check(self._L.rcsh_dynamics_derivatives(self.sim._h, _lib.ptr(rows), _lib.ptr(v), _lib.ptr(a), _lib.ptr(f), m, C.byref(out)))
+        return arrays
+
 
 @dataclass
 class SimGripperConfig:  # reference src/sim/SimGripper.h:15-45
