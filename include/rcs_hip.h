@@ -442,6 +442,63 @@ int rcsh_env_dynamics_derivatives(rcsh_sim* sim, const double* qacc_in, const do
 int rcsh_env_dynamics_derivatives_dev(rcsh_sim* sim, const double* qacc_in_dev, const double* qfrc_in_dev,
                                       const rcsh_dynamics_grad_out* out_dev);
 
+/* ---- operational-space dynamics of the TCP (csrc/opspace_team.h): what a task-space controller forms from qM, qfrc_bias and jac,
+ * formed on the device for M rows at once, plus the TCP's velocity-product acceleration.  Rows q, qvel (NULL: zero) are [M][nl] as
+ * in rcsh_dynamics_query; like it the call reads and writes NO per-environment state and runs on the handle's stream.
+ * Definitions, per row, everything in the robot-base frame of `jac`, the TCP that of rcsh_dynamics_query for the same tcp_offset7:
+ *   J      `jac` [6][nl] with the rows NOT selected by task_mask set to zero (bit r selects row r; rows 0-2 linear, 3-5 angular);
+ *   Minv   the full chain's M^-1, the matrix rcsh_dynamics_derivatives returns as qM_inv: armature and the finger slides included;
+ *   b      qfrc_bias;
+ *   A      J Minv J^T + damping * I_sel, I_sel the identity on the selected rows; damping >= 0 is in the units of A's diagonal.
+ * Outputs (every pointer of rcsh_opspace_out may be NULL: not wanted; an output's bits do not depend on which others are asked for):
+ *   twist       [M][6]       J qvel;
+ *   jdot_qvel   [M][6]       the TCP's acceleration at qacc = 0: linear part the classical acceleration of the TCP point, d^2 p/dt^2,
+ *                            angular part d omega/dt, so that d(twist)/dt = J qacc + jdot_qvel.  Masked rows are zero.  Analytic.
+ *   lambda_inv  [M][6][6]    A.  Always defined.
+ *   lambda      [M][6][6]    A^-1 on the selected rows and columns, zero elsewhere;
+ *   jbar        [M][nl][6]   Minv J^T lambda, the dynamically consistent inverse of J;
+ *   op_bias     [M][6]       jbar^T b - lambda jdot_qvel: the task force for a task acceleration xacc is lambda xacc + op_bias;
+ *   null_proj   [M][nl][nl]  I - J^T jbar^T, used as tau = J^T F + null_proj tau0;
+ *   qfrc        [M][nl]      J^T (lambda xacc_des + op_bias) + null_proj qfrc_null.  Needs xacc_des [M][6]; qfrc_null [M][nl], NULL: zero;
+ *   status      [M] int32    0: fine.  1: A is not positive definite to working precision.
+ * The status rule: A restricted to the selected rows is factored L D L^T without pivoting; a row gets status 1 when some
+ * d_i <= RCSH_OPSPACE_REL_PIVOT * A_ii, when d_i is not finite, or when A_ii <= 0.  In a status-1 row every entry of lambda, jbar,
+ * op_bias, null_proj and qfrc is NaN; twist, jdot_qvel and lambda_inv are always written.
+ * Forces NOT included: as with the other dynamics queries no actuator, damping, gravity-compensation, limit, equality, friction or
+ * contact force enters.  qfrc cancels b in the task space only: the caller puts gravity compensation (or -qfrc_gravcomp, where the
+ * scene compensates already) into qfrc_null or adds it afterwards.
+ * rcsh_opspace_opts is a host struct in every form; NULL means the site itself, task_mask 0x3F and damping 0.
+ * RCSH_ERR_STATE: no robot attached.  RCSH_ERR_ARG: M < 0; a null q or a null `out` where M > 0; qfrc asked for without xacc_des;
+ * task_mask 0 or above 0x3F; a negative or non-finite damping; a zero-norm offset quaternion; a non-finite input entry (host forms
+ * only).  M = 0 does nothing.
+ * rcsh_env_opspace asks the same once per environment (M = n_envs) at the environment's own chain qpos and qvel; xacc_des is [N][6],
+ * qfrc_null [N][nl].  It writes nothing but its outputs. */
+#define RCSH_OPSPACE_REL_PIVOT 1e-10 /* the status rule's bound on d_i / A_ii: a specification, not a measurement */
+typedef struct rcsh_opspace_opts {
+  const double* tcp_offset7; /* x y z qx qy qz qw as in rcsh_dynamics_query; NULL: the site itself */
+  uint32_t task_mask;        /* bit r: row r of J is part of the task; 0x3F: all six */
+  double damping;            /* >= 0, added to A's selected diagonal */
+} rcsh_opspace_opts;
+typedef struct rcsh_opspace_out {
+  double* twist;      /* [M][6] */
+  double* jdot_qvel;  /* [M][6] */
+  double* lambda_inv; /* [M][6][6] */
+  double* lambda;     /* [M][6][6] */
+  double* jbar;       /* [M][nl][6] */
+  double* op_bias;    /* [M][6] */
+  double* null_proj;  /* [M][nl][nl] */
+  double* qfrc;       /* [M][nl]; needs xacc_des */
+  int32_t* status;    /* [M] */
+} rcsh_opspace_out;
+int rcsh_opspace_query(rcsh_sim* sim, const double* q, const double* qvel, const double* xacc_des, const double* qfrc_null, int32_t m,
+                       const rcsh_opspace_opts* opts, const rcsh_opspace_out* out);
+int rcsh_opspace_query_dev(rcsh_sim* sim, const double* q_dev, const double* qvel_dev, const double* xacc_des_dev,
+                           const double* qfrc_null_dev, int32_t m, const rcsh_opspace_opts* opts, const rcsh_opspace_out* out_dev);
+int rcsh_env_opspace(rcsh_sim* sim, const double* xacc_des, const double* qfrc_null, const rcsh_opspace_opts* opts,
+                     const rcsh_opspace_out* out);
+int rcsh_env_opspace_dev(rcsh_sim* sim, const double* xacc_des_dev, const double* qfrc_null_dev, const rcsh_opspace_opts* opts,
+                         const rcsh_opspace_out* out_dev);
+
 /* SimGripper(sim, cfg) -- rcs.cpp:508-515, SimGripper.cpp:13-39 */
 int rcsh_sim_add_gripper(rcsh_sim* sim, const rcsh_gripper_desc* gripper);
 /* Gripper.set_normalized_width -- rcs.cpp:383-384, SimGripper.cpp:79-92 (RCSH_ERR_ARG outside [0,1] / force<0) */

@@ -26,6 +26,7 @@
 #include "swept_team.h"
 #include "dynamics_team.h"
 #include "dynamics_grad_team.h"
+#include "opspace_team.h"
 #include "guard_team.h"
 #include "episode_team.h"
 
@@ -1693,6 +1694,103 @@ int rcsh_env_dynamics_derivatives_dev(rcsh_sim* s, const double* qacc_in_dev, co
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (int rc = dynamics_grad_check(s->n, qacc_in_dev, qfrc_in_dev, out_dev)) return rc;
   return dynamics_grad_dev(s, nullptr, nullptr, qacc_in_dev, qfrc_in_dev, s->n, *out_dev, s->S.get());
+}
+
+// ---- operational-space dynamics (csrc/opspace_team.h)
+namespace {
+struct OpsCall {
+  double tcp_p[3];
+  uint32_t task_mask = 0x3F;
+  double damping = 0.0;
+};
+// what every form checks before anything is read; fills the TCP point, the mask and the damping
+int opspace_check(rcsh_sim* s, int32_t m, const double* xacc_des, const rcsh_opspace_opts* opts, const rcsh_opspace_out* out, OpsCall& c) {
+  if (m < 0) return fail(RCSH_ERR_ARG, "negative query count");
+  if (m > 0 && !out) return fail(RCSH_ERR_ARG, "null argument");
+  if (out && out->qfrc && !xacc_des) return fail(RCSH_ERR_ARG, "qfrc asked for without xacc_des");
+  if (opts) {
+    if (opts->task_mask == 0 || opts->task_mask > 0x3Fu) return fail(RCSH_ERR_ARG, "task_mask outside 0x01 .. 0x3F");
+    if (!(opts->damping >= 0.0) || !std::isfinite(opts->damping)) return fail(RCSH_ERR_ARG, "damping negative or non-finite");
+    c.task_mask = opts->task_mask;
+    c.damping = opts->damping;
+  }
+  // the TCP of the dynamics queries for the same offset (and their errors for a bad one)
+  return dynamics_check(s, 0, nullptr, nullptr, opts ? opts->tcp_offset7 : nullptr, nullptr, c.tcp_p);
+}
+// device pointers in; S non-null: the environments' own rows (m = n_envs)
+int opspace_dev(rcsh_sim* s, const double* q, const double* qvel, const double* xacc_des, const double* qfrc_null, int32_t m, const OpsCall& c,
+                const rcsh_opspace_out& o, const double* S) {
+  OpsArgs A{};
+  A.links = reinterpret_cast<const LinkRec*>(reinterpret_cast<const char*>(s->d_model.get()) + sizeof(DevModel));
+  A.m = m;
+  A.site_link = s->dm.site_link;
+  A.task_mask = c.task_mask;
+  A.damping = c.damping;
+  A.rel_pivot = RCSH_OPSPACE_REL_PIVOT;
+  for (int k = 0; k < 3; ++k) { A.gravity[k] = s->dm.gravity[k]; A.tcp_p[k] = c.tcp_p[k]; }
+  const double bq[4] = {s->dm.base_quat[1], s->dm.base_quat[2], s->dm.base_quat[3], s->dm.base_quat[0]};
+  quat_to_mat(bq, A.base_R);
+  A.q = q; A.qvel = qvel; A.xacc_des = xacc_des; A.qfrc_null = qfrc_null;
+  A.o = OpsOut{o.twist, o.jdot_qvel, o.lambda_inv, o.lambda, o.jbar, o.op_bias, o.null_proj, o.qfrc, o.status};
+  A.S = S; A.qpos_field = field_of(s, "qpos"); A.qvel_field = field_of(s, "qvel");
+  return team_launch(s, m, "operational-space query", [&](auto topo, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(k_opspace_query<decltype(topo)>, grid, block, 0, s->stream, A);
+  });
+}
+// the host form of both: q null: the environments' own rows
+int opspace_host(rcsh_sim* s, const double* q, const double* qvel, const double* xacc_des, const double* qfrc_null, int32_t m, const OpsCall& c,
+                 const rcsh_opspace_out& o, const double* S) {
+  const size_t nl = (size_t)s->nl, n = (size_t)m, row = n * nl, six = n * kTaskRows;
+  const double* in[4] = {q, qvel, o.qfrc ? xacc_des : nullptr, o.qfrc ? qfrc_null : nullptr};
+  const size_t count[4] = {row, row, six, row};
+  const char* names[4] = {"q", "qvel", "xacc_des", "qfrc_null"};
+  for (int k = 0; k < 4; ++k)
+    if (in[k])
+      if (int rc = query_finite(in[k], count[k], names[k])) return rc;
+  StageLayout L;
+  const auto dq = L.in(in[0], row), dv = L.in(in[1], row), dx = L.in(in[2], six), dn = L.in(in[3], row);
+  const auto d0 = L.out(o.twist, six), d1 = L.out(o.jdot_qvel, six), d2 = L.out(o.lambda_inv, six * kTaskRows), d3 = L.out(o.lambda, six * kTaskRows);
+  const auto d4 = L.out(o.jbar, row * kTaskRows), d5 = L.out(o.op_bias, six), d6 = L.out(o.null_proj, row * nl), d7 = L.out(o.qfrc, row);
+  const auto d8 = L.out(o.status, n);
+  return staged_call(s, s->d_query, L, [&](auto dev) {
+    rcsh_opspace_out od{};
+    od.twist = dev(d0); od.jdot_qvel = dev(d1); od.lambda_inv = dev(d2); od.lambda = dev(d3); od.jbar = dev(d4); od.op_bias = dev(d5);
+    od.null_proj = dev(d6); od.qfrc = dev(d7); od.status = dev(d8);
+    return opspace_dev(s, dev(dq), dev(dv), dev(dx), dev(dn), m, c, od, S);
+  });
+}
+}  // namespace
+
+int rcsh_opspace_query(rcsh_sim* s, const double* q, const double* qvel, const double* xacc_des, const double* qfrc_null, int32_t m,
+                       const rcsh_opspace_opts* opts, const rcsh_opspace_out* out) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  OpsCall c;
+  if (int rc = opspace_check(s, m, xacc_des, opts, out, c)) return rc;
+  if (m == 0) return RCSH_OK;
+  if (!q) return fail(RCSH_ERR_ARG, "null argument");
+  return opspace_host(s, q, qvel, xacc_des, qfrc_null, m, c, *out, nullptr);
+}
+int rcsh_opspace_query_dev(rcsh_sim* s, const double* q_dev, const double* qvel_dev, const double* xacc_des_dev, const double* qfrc_null_dev,
+                           int32_t m, const rcsh_opspace_opts* opts, const rcsh_opspace_out* out_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  OpsCall c;
+  if (int rc = opspace_check(s, m, xacc_des_dev, opts, out_dev, c)) return rc;
+  if (m == 0) return RCSH_OK;
+  if (!q_dev) return fail(RCSH_ERR_ARG, "null argument");
+  return opspace_dev(s, q_dev, qvel_dev, xacc_des_dev, qfrc_null_dev, m, c, *out_dev, nullptr);
+}
+int rcsh_env_opspace(rcsh_sim* s, const double* xacc_des, const double* qfrc_null, const rcsh_opspace_opts* opts, const rcsh_opspace_out* out) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  OpsCall c;
+  if (int rc = opspace_check(s, s->n, xacc_des, opts, out, c)) return rc;
+  return opspace_host(s, nullptr, nullptr, xacc_des, qfrc_null, s->n, c, *out, s->S.get());
+}
+int rcsh_env_opspace_dev(rcsh_sim* s, const double* xacc_des_dev, const double* qfrc_null_dev, const rcsh_opspace_opts* opts,
+                         const rcsh_opspace_out* out_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  OpsCall c;
+  if (int rc = opspace_check(s, s->n, xacc_des_dev, opts, out_dev, c)) return rc;
+  return opspace_dev(s, nullptr, nullptr, xacc_des_dev, qfrc_null_dev, s->n, c, *out_dev, s->S.get());
 }
 
 int rcsh_robot_get_state(rcsh_sim* s, uint8_t* ik_success, uint8_t* collision, uint8_t* is_moving, uint8_t* is_arrived,

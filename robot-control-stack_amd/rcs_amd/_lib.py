@@ -184,6 +184,18 @@ class DynamicsGradOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("dqfrc_inverse_dq", "dqfrc_inverse_dqvel", "dqacc_dq", "dqacc_dqvel", "qM_inv")]
 
 
+class OpspaceOpts(C.Structure):
+    """Options of the operational-space queries (rcsh_opspace_opts): a host struct in every form.  ``tcp_offset7``: host address of
+    x y z qx qy qz qw (NULL: the site itself)."""
+    _fields_ = [("tcp_offset7", C.c_void_p), ("task_mask", C.c_uint32), ("damping", C.c_double)]
+
+
+class OpspaceOut(C.Structure):
+    """Output pointers of the operational-space queries (rcsh_opspace_out): host arrays, or device addresses for the _dev forms; NULL:
+    not wanted.  ``status`` is int32 [M], the others double."""
+    _fields_ = [(name, C.c_void_p) for name in ("twist", "jdot_qvel", "lambda_inv", "lambda", "jbar", "op_bias", "null_proj", "qfrc", "status")]
+
+
 class SweptOut(C.Structure):
     """Output pointers of the swept clearance queries (rcsh_swept_out): host arrays, or device addresses for the _dev forms; NULL: not
     wanted (``distance`` is required)."""
@@ -223,6 +235,7 @@ EXPORTS = (
     "rcsh_swept_clearance", "rcsh_swept_clearance_dev", "rcsh_env_swept_clearance", "rcsh_env_swept_clearance_dev",
     "rcsh_dynamics_query", "rcsh_dynamics_query_dev", "rcsh_env_dynamics", "rcsh_env_dynamics_dev",
     "rcsh_dynamics_derivatives", "rcsh_dynamics_derivatives_dev", "rcsh_env_dynamics_derivatives", "rcsh_env_dynamics_derivatives_dev",
+    "rcsh_opspace_query", "rcsh_opspace_query_dev", "rcsh_env_opspace", "rcsh_env_opspace_dev",
     "rcsh_env_configure_guard", "rcsh_env_guard_peek", "rcsh_env_guard_peek_dev", "rcsh_env_guard_last", "rcsh_env_guard_last_dev",
     "rcsh_env_configure_autoreset", "rcsh_env_autoreset_record_dev", "rcsh_env_autoreset_last", "rcsh_autoreset_draw",
 )
@@ -323,6 +336,10 @@ def load() -> C.CDLL:
         fn.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32, C.POINTER(DynamicsGradOut)]
     for fn in (L.rcsh_env_dynamics_derivatives, L.rcsh_env_dynamics_derivatives_dev):
         fn.argtypes = [C.c_void_p] + [C.c_void_p] * 2 + [C.POINTER(DynamicsGradOut)]
+    for fn in (L.rcsh_opspace_query, L.rcsh_opspace_query_dev):
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32, C.POINTER(OpspaceOpts), C.POINTER(OpspaceOut)]
+    for fn in (L.rcsh_env_opspace, L.rcsh_env_opspace_dev):
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 2 + [C.POINTER(OpspaceOpts), C.POINTER(OpspaceOut)]
     L.rcsh_env_configure_guard.argtypes = [C.c_void_p, C.POINTER(GuardDesc)]
     for fn in (L.rcsh_env_guard_peek, L.rcsh_env_guard_peek_dev):
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

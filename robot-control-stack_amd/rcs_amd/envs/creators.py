@@ -249,6 +249,19 @@ class VecSimEnv:
         _lib.check(self._L.rcsh_env_dynamics_derivatives(self.sim._h, _lib.ptr(a), _lib.ptr(f), C.byref(out)))
         return arrays
 
+    def opspace(self, xacc=None, qfrc_null=None, tcp_offset=None, task_mask=0x3F, damping=0.0, want=None) -> dict:
+        """Every environment's operational-space dynamics where it is now: its own chain ``qpos`` and ``qvel``.  ``xacc`` [N, 6],
+        ``qfrc_null`` [N, nl], ``tcp_offset``, ``task_mask``, ``damping``, ``want`` and the returned dict of arrays as
+        :meth:`rcs_amd.sim.SimRobot.opspace_query`.  Reads the state, writes none of it."""
+        n, nl = self.n_envs, int(self.sim.model.nq)
+        want = self.robot._opspace_want(want, xacc)
+        rows = lambda a, w: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (n, w)))  # noqa: E731
+        x, f = rows(xacc, 6), rows(qfrc_null, nl)
+        arrays, out = self.robot._opspace_buffers(want, n, nl)
+        opts, _keep = self.robot._opspace_opts(tcp_offset, task_mask, damping)
+        _lib.check(self._L.rcsh_env_opspace(self.sim._h, _lib.ptr(x), _lib.ptr(f), C.byref(opts), C.byref(out)))
+        return arrays
+
     def _guard_info(self, i: dict[str, Any]):
         """info["guard_*"] of a guarded step; returns ``blocked`` where it truncates (else None)."""
         if not self.guard_enabled:

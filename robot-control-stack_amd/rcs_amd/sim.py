@@ -750,6 +750,57 @@ class SimRobot:
         _lib.check(self._L.rcsh_dynamics_derivatives(self.sim._h, _lib.ptr(rows), _lib.ptr(v), _lib.ptr(a), _lib.ptr(f), m, C.byref(out)))
         return arrays
 
+    # outputs of the operational-space queries, in the order of rcsh_opspace_out
+    OPSPACE_OUTPUTS = ("twist", "jdot_qvel", "lambda_inv", "lambda", "jbar", "op_bias", "null_proj", "qfrc", "status")
+
+    def _opspace_want(self, want, xacc) -> tuple:
+        if want is None:
+            want = tuple(k for k in self.OPSPACE_OUTPUTS if k != "qfrc" or xacc is not None)
+        want = (want,) if isinstance(want, str) else tuple(want)
+        unknown = [k for k in want if k not in self.OPSPACE_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown operational-space output {unknown}: one of {self.OPSPACE_OUTPUTS}")
+        return want
+
+    def _opspace_buffers(self, want, m: int, nl: int):
+        shape = {"twist": (m, 6), "jdot_qvel": (m, 6), "lambda_inv": (m, 6, 6), "lambda": (m, 6, 6), "jbar": (m, nl, 6), "op_bias": (m, 6),
+                 "null_proj": (m, nl, nl), "qfrc": (m, nl), "status": (m,)}
+        arrays = {k: np.zeros(shape[k], dtype=np.int32 if k == "status" else np.float64) for k in want}
+        return arrays, _lib.OpspaceOut(**{k: a.ctypes.data for k, a in arrays.items()})
+
+    @staticmethod
+    def _opspace_opts(tcp_offset, task_mask, damping):
+        """(rcsh_opspace_opts, the array its pointer refers to -- to be kept alive through the call)."""
+        tcp = DeviceKinematics._tcp(tcp_offset)
+        mask = int(task_mask)
+        if not 0 <= mask <= 0xFFFFFFFF:
+            raise ValueError(f"task_mask {task_mask}: bits 0-5 select the task rows")
+        return _lib.OpspaceOpts(tcp_offset7=None if tcp is None else tcp.ctypes.data, task_mask=mask, damping=float(damping)), tcp
+
+    def opspace_query(self, q, qvel=None, xacc=None, qfrc_null=None, tcp_offset=None, task_mask=0x3F, damping=0.0, want=None,
+                      finger_qpos=None) -> dict:
+        """Operational-space dynamics of the TCP for M caller-supplied states at once, without touching any environment's state: what a
+        task-space controller forms from ``qM``, ``qfrc_bias`` and ``jac`` of :meth:`dynamics_query`, formed on the device.
+
+        q, qvel: as in :meth:`dynamics_query`.  ``task_mask``: bit r selects row r of the Jacobian (0-2 linear, 3-5 angular);
+        ``damping`` >= 0 is added to the selected diagonal of ``lambda_inv``; ``tcp_offset`` as in :meth:`dynamics_query`.  ``want``:
+        names out of ``OPSPACE_OUTPUTS`` (None: every output the inputs allow).  Returns a dict of arrays, base frame: ``twist`` [M, 6] =
+        J qvel, ``jdot_qvel`` [M, 6] the TCP's acceleration at qacc = 0, ``lambda_inv`` [M, 6, 6] = J M^-1 J^T + damping I,
+        ``lambda`` its inverse on the selected rows, ``jbar`` [M, nl, 6] = M^-1 J^T lambda, ``op_bias`` [M, 6] = jbar^T qfrc_bias -
+        lambda jdot_qvel, ``null_proj`` [M, nl, nl] = I - J^T jbar^T, ``qfrc`` [M, nl] = J^T (lambda xacc + op_bias) + null_proj
+        qfrc_null (needs ``xacc`` [M, 6]; ``qfrc_null`` None: zero) and ``status`` [M] int32 (1: ``lambda_inv`` is not positive
+        definite to working precision, and the five outputs from ``lambda`` to ``qfrc`` are NaN).  No gravity compensation enters
+        ``qfrc``: put it into ``qfrc_null`` or add it afterwards (include/rcs_hip.h, rcsh_opspace_query)."""
+        want = self._opspace_want(want, xacc)
+        rows = self._query_rows(q, finger_qpos, "q")
+        m, nl = rows.shape
+        like = lambda x, w: None if x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (m, w)))  # noqa: E731
+        v, x, f = like(qvel, nl), like(xacc, 6), like(qfrc_null, nl)
+        arrays, out = self._opspace_buffers(want, m, nl)
+        opts, _keep = self._opspace_opts(tcp_offset, task_mask, damping)
+        _lib.check(self._L.rcsh_opspace_query(self.sim._h, _lib.ptr(rows), _lib.ptr(v), _lib.ptr(x), _lib.ptr(f), m, C.byref(opts), C.byref(out)))
+        return arrays
+
 
 @dataclass
 class SimGripperConfig:  # reference src/sim/SimGripper.h:15-45
