@@ -499,6 +499,59 @@ int rcsh_env_opspace(rcsh_sim* sim, const double* xacc_des, const double* qfrc_n
 int rcsh_env_opspace_dev(rcsh_sim* sim, const double* xacc_des_dev, const double* qfrc_null_dev, const rcsh_opspace_opts* opts,
                          const rcsh_opspace_out* out_dev);
 
+/* ---- torque control (csrc/torque_team.h).  A robot is TORQUE-ACTUATED when every arm actuator has biastype none and a zero biasprm
+ * (MJCF <motor>; rcs_amd.mjcf.torque_actuated_scene writes such a variant of a shipped scene): its ctrl is a joint torque, clamped by
+ * ctrlrange and the joint's actuatorfrcrange like any ctrl.  A mixed arm is not torque-actuated.
+ * rcsh_robot_set_joint_torque writes the arm's ctrl ([N][dof]) of the masked environments and nothing else: target, previous angles,
+ * the moving / arrived flags and the gripper's ctrl stay.  RCSH_ERR_ARG on a robot that is not torque-actuated.
+ * On a torque-actuated robot rcsh_sim_step holds ctrl over the launch as ever; rcsh_sim_step_until_convergence and
+ * rcsh_robot_set_cartesian_position return RCSH_ERR_ARG (the predicates and the CLIK assume position servos);
+ * rcsh_robot_set_joint_position, rcsh_robot_move_home, rcsh_robot_reset and rcsh_robot_set_joints_hard write target / previous
+ * angles / qpos as before but ZERO to the arm's ctrl, and set the law's targets to that configuration and its TCP pose.
+ *
+ * The law at substep rate.  rcsh_sim_step_torque(k) runs k substeps in one launch and evaluates, before each, at the state the substep
+ * starts on (robot-base frame; TCP, Jacobian and every term as rcsh_dynamics_query / rcsh_opspace_query define them for tcp_offset7,
+ * task_mask and damping):
+ *   x_err     = [p_des - p ; rotvec(R_des R^T)]                 rotvec: the rotation vector on the shorter arc
+ *   xacc      = task_k * x_err - task_d * twist                 (diagonal gains, on the task acceleration)
+ *   qfrc_null = joint_k * (q_des - q) - joint_d * qvel  (+ qfrc_bias if compensate_bias)       finger entries: 0 (+ qfrc_bias)
+ *   tau       = J^T (lambda xacc + op_bias) + null_proj qfrc_null - qfrc_gravcomp
+ *   ctrl[arm] = tau[arm]                                        (the finger entries are dropped; the gripper's ctrl is the caller's)
+ * task_mask = 0 is the pure joint law: tau = qfrc_null - qfrc_gravcomp.  enabled = 0: no law, ctrl is the caller's.
+ * Where the opspace status would be 1 the substep keeps the torque of the substep before and the environment's `singular` byte is
+ * raised (rcsh_torque_status; sticky until rcsh_sim_reset / rcsh_robot_reset of that environment); no NaN reaches ctrl: a torque
+ * that comes out non-finite (a NaN or zero-quaternion target written through the _dev form, which validates nothing) is held back
+ * the same way.  The pose targets that the resets and set_joint_position leave are formed with the tcp_offset7 configured at that
+ * moment (before any rcsh_torque_configure: the site itself): after configuring another offset, set the targets again.
+ * rcsh_sim_step_torque runs no position-servo bookkeeping: the is_moving / is_arrived callbacks and their timestamps stay as they
+ * were while `time` advances, so a later rcsh_sim_step fires them against the old timestamps.
+ * After the launch ctrl holds the last torque applied (rcsh_sim_get_ctrl), and the launch ends with the handle's check for contacts
+ * nobody resolves, as rcsh_sim_step does.
+ * rcsh_torque_set_target: pose7 [N][7] (x y z qx qy qz qw, base frame) and / or q_des [N][dof]; NULL keeps; masked.
+ * RCSH_ERR_ARG from rcsh_torque_configure and rcsh_sim_step_torque: the robot is not torque-actuated, the scene has a free body,
+ * robot contacts are resolved, rate-driven cameras are scheduled, the site is static; a task_mask above 0x3F, a negative or
+ * non-finite damping or gain, a zero-norm offset quaternion; k < 0.  RCSH_ERR_STATE: no robot.  RCSH_ERR_MODEL: no kernel for the
+ * archetype (dry joint friction other than on the 7-dof arm without gripper). */
+#define RCSH_MAX_ARM 8
+typedef struct rcsh_torque_law {
+  int32_t enabled;        /* 0: ctrl is the caller's (rcsh_robot_set_joint_torque) */
+  uint32_t task_mask;     /* as rcsh_opspace_opts; 0: pure joint law */
+  double damping;         /* as rcsh_opspace_opts */
+  double tcp_offset7[7];  /* x y z qx qy qz qw as in rcsh_dynamics_query; all zero: the site itself */
+  double task_k[6], task_d[6];                       /* diagonal, on the task acceleration, robot-base frame */
+  double joint_k[RCSH_MAX_ARM], joint_d[RCSH_MAX_ARM]; /* null-space / joint impedance */
+  int32_t compensate_bias; /* add qfrc_bias to the null-space torque */
+} rcsh_torque_law;
+int rcsh_robot_is_torque_actuated(rcsh_sim* sim, int32_t* yes);
+int rcsh_robot_set_joint_torque(rcsh_sim* sim, const double* tau /*[N][dof]*/, const uint8_t* mask);
+int rcsh_robot_set_joint_torque_dev(rcsh_sim* sim, const double* tau_dev, const uint8_t* mask_dev);
+int rcsh_torque_configure(rcsh_sim* sim, const rcsh_torque_law* law);
+int rcsh_torque_set_target(rcsh_sim* sim, const double* pose7, const double* q_des, const uint8_t* mask);
+int rcsh_torque_set_target_dev(rcsh_sim* sim, const double* pose7_dev, const double* q_des_dev, const uint8_t* mask_dev);
+int rcsh_torque_get_target(rcsh_sim* sim, double* pose7 /*[N][7]*/, double* q_des /*[N][dof]*/); /* either may be NULL */
+int rcsh_sim_step_torque(rcsh_sim* sim, int64_t k);
+int rcsh_torque_status(rcsh_sim* sim, uint8_t* singular /*[N]*/);
+
 /* SimGripper(sim, cfg) -- rcs.cpp:508-515, SimGripper.cpp:13-39 */
 int rcsh_sim_add_gripper(rcsh_sim* sim, const rcsh_gripper_desc* gripper);
 /* Gripper.set_normalized_width -- rcs.cpp:383-384, SimGripper.cpp:79-92 (RCSH_ERR_ARG outside [0,1] / force<0) */

@@ -27,6 +27,7 @@
 #include "dynamics_team.h"
 #include "dynamics_grad_team.h"
 #include "opspace_team.h"
+#include "torque_team.h"
 #include "guard_team.h"
 #include "episode_team.h"
 
@@ -166,6 +167,14 @@ struct rcsh_sim {
   BoxCfg box{};
   TaskCfg task{};
   bool env_configured = false;
+  // torque control (torque_team.h): whether every arm actuator is a plain torque source (settled by rcsh_sim_add_robot), the law as last
+  // configured, and -- one group, allocated at the first use -- the law's targets and the environments' sticky `singular` bytes
+  struct Torque {
+    bool actuated = false;
+    rcsh_torque_law law{};
+    DevBuf<double> target;     // [kTorquePose + narm][n]
+    DevBuf<uint8_t> singular;  // [n]
+  } tq;
   DevBuf<BoxTaskCfg> d_boxtask;
   // depth renderer (render.h)
   RenderScene rscene{};              // its pointers are views into rbuf (rcsh_sim_set_render_scene, rcsh_sim_set_render_colours)
@@ -783,6 +792,109 @@ QueryPairs query_pairs(rcsh_sim* s, int32_t kinds, bool with_ids = true) {
 #define REQUIRE_GRIPPER(s) \
   if (!(s)->gripcfg.present) return fail(RCSH_ERR_STATE, "no gripper attached: call rcsh_sim_add_gripper first")
 
+// ---- torque control (csrc/torque_team.h)
+static_assert(RCSH_MAX_ARM == kMaxArm, "rcsh_torque_law's gain rows are the model's arm bound");
+#define REQUIRE_TORQUE(s, what) \
+  if (!(s)->tq.actuated) return fail(RCSH_ERR_ARG, std::string(what) + ": the robot is not torque-actuated (an arm actuator has a bias: a servo)")
+// the targets and the singular bytes, zeroed, at their first use
+int torque_buffers(rcsh_sim* s) {
+  if (s->tq.target) return RCSH_OK;
+  const size_t n = (size_t)s->n, w = (size_t)(kTorquePose + s->narm);
+  DevBuf<double> tg;
+  DevBuf<uint8_t> sg;
+  HIP_TRY(hipMalloc(tg.out(), sizeof(double) * w * n));
+  HIP_TRY(hipMalloc(sg.out(), n));
+  HIP_TRY(hipMemsetAsync(tg.get(), 0, sizeof(double) * w * n, s->stream));
+  HIP_TRY(hipMemsetAsync(sg.get(), 0, n, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  s->tq.target = std::move(tg);
+  s->tq.singular = std::move(sg);
+  return RCSH_OK;
+}
+// what the torque kernels are handed: the law with its TCP resolved into the site link's frame -- the pose rcsh_ik_forward reports is
+// site * offset^-1 (quirk Q7), as the dynamics queries take it
+TorqueArgs torque_args(rcsh_sim* s, const rcsh_torque_law& law, int32_t k) {
+  TorqueArgs A{};
+  A.model = s->d_model.get();
+  A.S = s->S.get();
+  A.n = s->n;
+  A.k = k;
+  A.keep_qpre = bool(s->rbuf.frames);
+  A.enabled = law.enabled;
+  A.target = s->tq.target.get();
+  A.singular = s->tq.singular.get();
+  TorqueLawDev& d = A.law;
+  d.task_mask = law.task_mask;
+  d.compensate_bias = law.compensate_bias;
+  d.damping = law.damping;
+  d.rel_pivot = RCSH_OPSPACE_REL_PIVOT;
+  const double* o = law.tcp_offset7;
+  const double nq = std::sqrt(o[3] * o[3] + o[4] * o[4] + o[5] * o[5] + o[6] * o[6]);
+  double Roff[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, off[3] = {0, 0, 0};
+  if (nq > 0.0) {
+    const double qn[4] = {o[3] / nq, o[4] / nq, o[5] / nq, o[6] / nq};
+    quat_to_mat(qn, Roff);
+    for (int c = 0; c < 3; ++c) off[c] = -(Roff[c] * o[0] + Roff[3 + c] * o[1] + Roff[6 + c] * o[2]);
+  }
+  const double* sr = s->dm.site_rot;
+  for (int r = 0; r < 3; ++r) {
+    d.tcp_p[r] = s->dm.site_pos[r] + sr[3 * r] * off[0] + sr[3 * r + 1] * off[1] + sr[3 * r + 2] * off[2];
+    for (int c = 0; c < 3; ++c) d.tcp_R[3 * r + c] = sr[3 * r] * Roff[3 * c] + sr[3 * r + 1] * Roff[3 * c + 1] + sr[3 * r + 2] * Roff[3 * c + 2];  // site_rot Roff^T
+    d.base_p[r] = s->dm.base_pos[r];
+  }
+  const double bq[4] = {s->dm.base_quat[1], s->dm.base_quat[2], s->dm.base_quat[3], s->dm.base_quat[0]};
+  quat_to_mat(bq, d.base_R);
+  for (int r = 0; r < kTaskRows; ++r) { d.task_k[r] = law.task_k[r]; d.task_d[r] = law.task_d[r]; }
+  for (int i = 0; i < kMaxArm; ++i) { d.joint_k[i] = law.joint_k[i]; d.joint_d[i] = law.joint_d[i]; }
+  return A;
+}
+// why the fused launch does not serve this handle (empty: it does)
+std::string torque_scope(const rcsh_sim* s) {
+  if (!s->tq.actuated) return "the robot is not torque-actuated (an arm actuator has a bias: a servo)";
+  if (s->box.present) return "the scene has a free body";
+  if (s->box.resolve) return "robot contacts are resolved (rcsh_sim_set_contact_options)";
+  if (s->rend.ncam > 0) return "rate-driven cameras are scheduled (rcsh_sim_set_render_schedule)";
+  if (s->dm.site_link < 0) return "the attachment site is static";
+  return "";
+}
+// q_des (device, [n][narm], null: keep) and / or pose7 (device, [n][7], null: keep) into the targets of the masked environments
+int torque_target_dev(rcsh_sim* s, const double* pose7, const double* q_des, const uint8_t* mask_dev) {
+  if (int rc = torque_buffers(s)) return rc;
+  if (pose7) hipLaunchKernelGGL(k_scatter, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->tq.target.get(), s->n, 0, kTorquePose, pose7, mask_dev);
+  if (q_des) hipLaunchKernelGGL(k_scatter, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->tq.target.get(), s->n, kTorquePose, s->narm, q_des, mask_dev);
+  HIP_TRY(hipGetLastError());
+  return RCSH_OK;
+}
+// A torque-actuated robot after set_joint_position / move_home / a reset to q (host, [n][narm]): zero torque, and the law's targets at
+// that configuration and its TCP pose.  `clear`: the singular bytes of the masked environments too (the resets).
+int torque_rest_at(rcsh_sim* s, const double* q, const uint8_t* mask, bool clear) {
+  if (int rc = torque_buffers(s)) return rc;
+  std::vector<double> z((size_t)s->n * s->narm, 0.0);
+  int rc = scatter_host(s, field_of(s, "ctrl"), s->narm, z.data(), mask);
+  if (rc) return rc;
+  const uint8_t* dm = nullptr;
+  if ((rc = upload_mask(s, mask, &dm))) return rc;
+  HIP_TRY(hipMemcpyAsync(s->stage.wide, q, sizeof(double) * s->n * s->narm, hipMemcpyHostToDevice, s->stream));
+  if ((rc = torque_target_dev(s, nullptr, s->stage.wide, dm))) return rc;
+  TorqueArgs A = torque_args(s, s->tq.law, 0);
+  rc = team_launch(s, s->n, "torque target pose", [&](auto topo, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(k_torque_target_pose<decltype(topo)>, grid, block, 0, s->stream, A, dm);
+  });
+  if (rc) return rc;
+  if (clear) {
+    if (!mask) HIP_TRY(hipMemsetAsync(s->tq.singular.get(), 0, s->n, s->stream));
+    else {
+      std::vector<uint8_t> sg(s->n);
+      HIP_TRY(hipMemcpyAsync(sg.data(), s->tq.singular.get(), s->n, hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(hipStreamSynchronize(s->stream));
+      for (int e = 0; e < s->n; ++e) sg[e] = mask[e] ? 0 : sg[e];
+      HIP_TRY(hipMemcpyAsync(s->tq.singular.get(), sg.data(), s->n, hipMemcpyHostToDevice, s->stream));
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RCSH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -936,6 +1048,7 @@ int rcsh_sim_step(rcsh_sim* s, int64_t k) {
 
 int rcsh_sim_step_until_convergence(rcsh_sim* s) {
   REQUIRE_SIM(s);
+  if (s->tq.actuated) return fail(RCSH_ERR_ARG, "step_until_convergence: the robot is torque-actuated; the convergence predicates assume position servos");
   RunOp op{};
   op.nsteps = -1;
   int rc = launch_run(s, op, false);
@@ -970,6 +1083,13 @@ int rcsh_sim_reset(rcsh_sim* s, const uint8_t* mask) {
   if (!rc) rc = scatter_host(s, field_of(s, "xs"), s->nl, z.data(), mask);  // (mj_resetData: qacc_warmstart := 0)
   if (!rc) rc = flags_update_host(s, 0, kContactOverflow | kContactUnresolved | kContactResolved | kEscQuiet, mask);
   if (!rc) rc = scatter_host(s, field_of(s, "sep"), kCheckSep, z.data(), mask);
+  if (!rc && s->tq.actuated && s->robot.present) {
+    // a torque-actuated robot: the law's targets go to the reset configuration and its pose, the singular bytes are cleared
+    std::vector<double> qa((size_t)s->n * s->narm);
+    for (int e = 0; e < s->n; ++e)
+      for (int i = 0; i < s->narm; ++i) qa[(size_t)e * s->narm + i] = s->dm.qpos0[i];
+    rc = torque_rest_at(s, qa.data(), mask, true);
+  }
   if (!rc && s->esc.mask) {
     // per-environment escalation: a reset environment starts over on the lean kernel
     const size_t nw = ((size_t)s->n + 63) / 64;
@@ -1047,20 +1167,33 @@ int rcsh_sim_add_robot(rcsh_sim* s, const rcsh_robot_desc* r) {
   rc = upload_coll_classes(s);
   if (!rc) rc = upload_contact_table(s);
   if (rc) return rc;
+  // torque-actuated: every arm actuator a plain torque source (biastype none, zero biasprm); a mixed arm is not
+  s->tq.actuated = true;
+  for (int i = 0; i < s->narm; ++i)
+    s->tq.actuated = s->tq.actuated && s->dm.arm_has_act[i] && !s->dm.arm_biasaffine[i] && s->dm.arm_bias[i][0] == 0.0 &&
+                     s->dm.arm_bias[i][1] == 0.0 && s->dm.arm_bias[i][2] == 0.0;
   return rcsh_robot_reset(s, nullptr);  // SimRobot ctor ends with m_reset()
 }
 
-int rcsh_robot_set_joints_hard(rcsh_sim* s, const double* q, const uint8_t* mask) {
-  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+namespace {
+// set_joints_hard; `reset`: on a torque-actuated robot the singular bytes of the masked environments are cleared too
+int joints_hard(rcsh_sim* s, const double* q, const uint8_t* mask, bool reset) {
   int rc = scatter_host(s, field_of(s, "qpos"), s->narm, q, mask);
+  if (!rc && s->tq.actuated) return torque_rest_at(s, q, mask, reset);  // (ctrl is a torque: zero, and the law's targets at q)
   if (!rc) rc = scatter_host(s, field_of(s, "ctrl"), s->narm, q, mask);
   return rc;
+}
+}  // namespace
+
+int rcsh_robot_set_joints_hard(rcsh_sim* s, const double* q, const uint8_t* mask) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  return joints_hard(s, q, mask, false);
 }
 
 int rcsh_robot_reset(rcsh_sim* s, const uint8_t* mask) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   std::vector<double> q = tile(s->robot.q_home, s->narm, s->n);
-  return rcsh_robot_set_joints_hard(s, q.data(), mask);
+  return joints_hard(s, q.data(), mask, true);
 }
 
 int rcsh_robot_set_joint_position(rcsh_sim* s, const double* q, const uint8_t* mask) {
@@ -1070,7 +1203,7 @@ int rcsh_robot_set_joint_position(rcsh_sim* s, const double* q, const uint8_t* m
   int rc = gather_host(s, field_of(s, "qpos"), s->narm, cur.data());
   if (!rc) rc = scatter_host(s, field_of(s, "target"), s->narm, q, mask);
   if (!rc) rc = scatter_host(s, field_of(s, "prevq"), s->narm, cur.data(), mask);
-  if (!rc) rc = scatter_host(s, field_of(s, "ctrl"), s->narm, q, mask);
+  if (!rc) rc = s->tq.actuated ? torque_rest_at(s, q, mask, false) : scatter_host(s, field_of(s, "ctrl"), s->narm, q, mask);
   if (!rc) rc = flags_update_host(s, kIsMoving, kIsArrived, mask);
   return rc;
 }
@@ -1133,6 +1266,7 @@ int launch_cartesian(rcsh_sim* s, const CartOp& op) {
 int rcsh_robot_set_cartesian_position(rcsh_sim* s, const double* pose, const uint8_t* mask) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!pose) return fail(RCSH_ERR_ARG, "null pose");
+  if (s->tq.actuated) return fail(RCSH_ERR_ARG, "set_cartesian_position: the robot is torque-actuated; the CLIK commands position servos");
   const uint8_t* dm = nullptr;
   int rc = upload_mask(s, mask, &dm);
   if (rc) return rc;
@@ -1791,6 +1925,125 @@ int rcsh_env_opspace_dev(rcsh_sim* s, const double* xacc_des_dev, const double* 
   OpsCall c;
   if (int rc = opspace_check(s, s->n, xacc_des_dev, opts, out_dev, c)) return rc;
   return opspace_dev(s, nullptr, nullptr, xacc_des_dev, qfrc_null_dev, s->n, c, *out_dev, s->S.get());
+}
+
+// ---- torque control (csrc/torque_team.h)
+int rcsh_robot_is_torque_actuated(rcsh_sim* s, int32_t* yes) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (!yes) return fail(RCSH_ERR_ARG, "null argument");
+  *yes = s->tq.actuated ? 1 : 0;
+  return RCSH_OK;
+}
+int rcsh_robot_set_joint_torque_dev(rcsh_sim* s, const double* tau_dev, const uint8_t* mask_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s); REQUIRE_TORQUE(s, "set_joint_torque");
+  if (!tau_dev) return fail(RCSH_ERR_ARG, "null argument");
+  hipLaunchKernelGGL(k_scatter, dim3(grid_for(s->n)), dim3(kBlock), 0, s->stream, s->S.get(), s->n, field_of(s, "ctrl"), s->narm, tau_dev, mask_dev);
+  HIP_TRY(hipGetLastError());
+  return RCSH_OK;
+}
+int rcsh_robot_set_joint_torque(rcsh_sim* s, const double* tau, const uint8_t* mask) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s); REQUIRE_TORQUE(s, "set_joint_torque");
+  if (!tau) return fail(RCSH_ERR_ARG, "null argument");
+  const size_t row = (size_t)s->n * s->narm;
+  if (int rc = query_finite(tau, row, "tau")) return rc;
+  StageLayout L;
+  const auto dt = L.in(tau, row);
+  const auto dk = L.in(mask, (size_t)s->n);
+  return staged_call(s, s->d_query, L, [&](auto dev) { return rcsh_robot_set_joint_torque_dev(s, dev(dt), dev(dk)); });
+}
+int rcsh_torque_configure(rcsh_sim* s, const rcsh_torque_law* law) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (!law) return fail(RCSH_ERR_ARG, "null argument");
+  if (const std::string why = torque_scope(s); !why.empty()) return fail(RCSH_ERR_ARG, "torque law: " + why);
+  if (law->task_mask > 0x3Fu) return fail(RCSH_ERR_ARG, "task_mask above 0x3F");
+  if (!(law->damping >= 0.0) || !std::isfinite(law->damping)) return fail(RCSH_ERR_ARG, "damping negative or non-finite");
+  if (int rc = query_finite(law->tcp_offset7, 7, "tcp_offset7")) return rc;
+  const double* o = law->tcp_offset7;
+  const bool none = o[0] == 0 && o[1] == 0 && o[2] == 0 && o[3] == 0 && o[4] == 0 && o[5] == 0 && o[6] == 0;
+  if (!none && !(o[3] * o[3] + o[4] * o[4] + o[5] * o[5] + o[6] * o[6] > 0.0)) return fail(RCSH_ERR_ARG, "tcp_offset7 quaternion of zero norm");
+  for (int r = 0; r < kTaskRows; ++r)
+    if (!(law->task_k[r] >= 0.0) || !(law->task_d[r] >= 0.0) || !std::isfinite(law->task_k[r]) || !std::isfinite(law->task_d[r]))
+      return fail(RCSH_ERR_ARG, "task gain negative or non-finite");
+  for (int i = 0; i < s->narm; ++i)
+    if (!(law->joint_k[i] >= 0.0) || !(law->joint_d[i] >= 0.0) || !std::isfinite(law->joint_k[i]) || !std::isfinite(law->joint_d[i]))
+      return fail(RCSH_ERR_ARG, "joint gain negative or non-finite");
+  if (int rc = torque_buffers(s)) return rc;
+  s->tq.law = *law;
+  return RCSH_OK;
+}
+int rcsh_torque_set_target_dev(rcsh_sim* s, const double* pose7_dev, const double* q_des_dev, const uint8_t* mask_dev) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s); REQUIRE_TORQUE(s, "torque target");
+  return torque_target_dev(s, pose7_dev, q_des_dev, mask_dev);
+}
+int rcsh_torque_set_target(rcsh_sim* s, const double* pose7, const double* q_des, const uint8_t* mask) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s); REQUIRE_TORQUE(s, "torque target");
+  const size_t n = (size_t)s->n;
+  if (pose7) {
+    if (int rc = query_finite(pose7, n * kTorquePose, "pose7")) return rc;
+    for (size_t e = 0; e < n; ++e) {
+      const double* q = pose7 + e * kTorquePose + 3;
+      if ((!mask || mask[e]) && !(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] > 0.0)) return fail(RCSH_ERR_ARG, "pose7 quaternion of zero norm");
+    }
+  }
+  if (q_des)
+    if (int rc = query_finite(q_des, n * s->narm, "q_des")) return rc;
+  StageLayout L;
+  const auto dp = L.in(pose7, n * kTorquePose), dq = L.in(q_des, n * (size_t)s->narm);
+  const auto dk = L.in(mask, n);
+  return staged_call(s, s->d_query, L, [&](auto dev) { return torque_target_dev(s, dev(dp), dev(dq), dev(dk)); });
+}
+int rcsh_torque_get_target(rcsh_sim* s, double* pose7, double* q_des) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s); REQUIRE_TORQUE(s, "torque target");
+  if (int rc = torque_buffers(s)) return rc;
+  const size_t n = (size_t)s->n, w = (size_t)(kTorquePose + s->narm);
+  std::vector<double> t(w * n);
+  HIP_TRY(hipMemcpyAsync(t.data(), s->tq.target.get(), sizeof(double) * w * n, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  for (size_t e = 0; e < n; ++e) {
+    if (pose7) for (int k = 0; k < kTorquePose; ++k) pose7[e * kTorquePose + k] = t[(size_t)k * n + e];
+    if (q_des) for (int i = 0; i < s->narm; ++i) q_des[e * s->narm + i] = t[(size_t)(kTorquePose + i) * n + e];
+  }
+  return RCSH_OK;
+}
+int rcsh_torque_status(rcsh_sim* s, uint8_t* singular) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s); REQUIRE_TORQUE(s, "torque status");
+  if (!singular) return fail(RCSH_ERR_ARG, "null argument");
+  if (int rc = torque_buffers(s)) return rc;
+  HIP_TRY(hipMemcpyAsync(singular, s->tq.singular.get(), s->n, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RCSH_OK;
+}
+int rcsh_sim_step_torque(rcsh_sim* s, int64_t k) {
+  REQUIRE_SIM(s); REQUIRE_ROBOT(s);
+  if (const std::string why = torque_scope(s); !why.empty()) return fail(RCSH_ERR_ARG, "step_torque: " + why);
+  if (k < 0 || k > 0x7fffffff) return fail(RCSH_ERR_ARG, "step count must be non-negative");
+  if (int rc = torque_buffers(s)) return rc;
+  if (k > 0) {
+    const TorqueArgs A = torque_args(s, s->tq.law, (int32_t)k);
+    bool launched = false;
+    int rc = team_launch(s, s->n, "step_torque", [&](auto topo, dim3 grid, dim3 block) {
+      using T = decltype(topo);
+      if (!s->dm.has_friction) {
+        hipLaunchKernelGGL((k_run_torque<T, false>), grid, block, 0, s->stream, A);
+        launched = true;
+      } else if constexpr (T::NARM == 7 && !T::GRIP) {
+        hipLaunchKernelGGL((k_run_torque<T, true>), grid, block, 0, s->stream, A);
+        launched = true;
+      }
+    });
+    if (rc) return rc;
+    if (!launched) return fail(RCSH_ERR_MODEL, "step_torque: no kernel instantiated for this archetype with dry joint friction");
+    // the end-of-launch check for contacts nobody resolves, at the handle's cadence: the zero-substep launch that asks for it alone
+    if (s->contact_check && s->check_every > 0 && (s->check_seq++ % s->check_every) == 0) {
+      RunOp op{};
+      op.nsteps = 0;
+      op.observe_only = 1;
+      op.check = 1;
+      if ((rc = launch_run(s, op, false))) return rc;
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return RCSH_OK;
 }
 
 int rcsh_robot_get_state(rcsh_sim* s, uint8_t* ik_success, uint8_t* collision, uint8_t* is_moving, uint8_t* is_arrived,

@@ -196,6 +196,13 @@ class OpspaceOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("twist", "jdot_qvel", "lambda_inv", "lambda", "jbar", "op_bias", "null_proj", "qfrc", "status")]
 
 
+class TorqueLaw(C.Structure):
+    """The substep-rate torque law (rcsh_torque_law): a host struct.  ``tcp_offset7`` all zero: the site itself."""
+    _fields_ = [("enabled", C.c_int32), ("task_mask", C.c_uint32), ("damping", C.c_double), ("tcp_offset7", C.c_double * 7),
+                ("task_k", C.c_double * 6), ("task_d", C.c_double * 6), ("joint_k", C.c_double * 8), ("joint_d", C.c_double * 8),
+                ("compensate_bias", C.c_int32)]
+
+
 class SweptOut(C.Structure):
     """Output pointers of the swept clearance queries (rcsh_swept_out): host arrays, or device addresses for the _dev forms; NULL: not
     wanted (``distance`` is required)."""
@@ -236,6 +243,8 @@ EXPORTS = (
     "rcsh_dynamics_query", "rcsh_dynamics_query_dev", "rcsh_env_dynamics", "rcsh_env_dynamics_dev",
     "rcsh_dynamics_derivatives", "rcsh_dynamics_derivatives_dev", "rcsh_env_dynamics_derivatives", "rcsh_env_dynamics_derivatives_dev",
     "rcsh_opspace_query", "rcsh_opspace_query_dev", "rcsh_env_opspace", "rcsh_env_opspace_dev",
+    "rcsh_robot_is_torque_actuated", "rcsh_robot_set_joint_torque", "rcsh_robot_set_joint_torque_dev", "rcsh_torque_configure",
+    "rcsh_torque_set_target", "rcsh_torque_set_target_dev", "rcsh_torque_get_target", "rcsh_sim_step_torque", "rcsh_torque_status",
     "rcsh_env_configure_guard", "rcsh_env_guard_peek", "rcsh_env_guard_peek_dev", "rcsh_env_guard_last", "rcsh_env_guard_last_dev",
     "rcsh_env_configure_autoreset", "rcsh_env_autoreset_record_dev", "rcsh_env_autoreset_last", "rcsh_autoreset_draw",
 )
@@ -340,6 +349,15 @@ def load() -> C.CDLL:
         fn.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32, C.POINTER(OpspaceOpts), C.POINTER(OpspaceOut)]
     for fn in (L.rcsh_env_opspace, L.rcsh_env_opspace_dev):
         fn.argtypes = [C.c_void_p] + [C.c_void_p] * 2 + [C.POINTER(OpspaceOpts), C.POINTER(OpspaceOut)]
+    L.rcsh_robot_is_torque_actuated.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    for fn in (L.rcsh_robot_set_joint_torque, L.rcsh_robot_set_joint_torque_dev):
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rcsh_torque_configure.argtypes = [C.c_void_p, C.POINTER(TorqueLaw)]
+    for fn in (L.rcsh_torque_set_target, L.rcsh_torque_set_target_dev):
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rcsh_torque_get_target.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rcsh_sim_step_torque.argtypes = [C.c_void_p, C.c_int64]
+    L.rcsh_torque_status.argtypes = [C.c_void_p, C.c_void_p]
     L.rcsh_env_configure_guard.argtypes = [C.c_void_p, C.POINTER(GuardDesc)]
     for fn in (L.rcsh_env_guard_peek, L.rcsh_env_guard_peek_dev):
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

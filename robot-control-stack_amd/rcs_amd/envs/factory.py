@@ -21,7 +21,22 @@ MAX_JOINT_MOV = float(np.deg2rad(5))
 ROBOTS = ("fr3", "xarm7", "xarm7_box", "xarm7_pick", "arm6", "ur5e", "so101")
 
 
-def robot_cfg_for(robot: str) -> sim.SimRobotConfig:
+def torque_actuated_cfg(cfg: sim.SimRobotConfig) -> sim.SimRobotConfig:
+    """A copy of `cfg` with its scene replaced by the torque-actuated variant (mjcf.torque_actuated_scene: the actuators of the
+    robot's own joints become `<motor>`s), written to the process's scratch directory."""
+    import copy
+
+    from ..mjcf import torque_actuated_scene
+
+    out = copy.copy(cfg)
+    src = str(cfg.mjcf_scene_path)
+    out.mjcf_scene_path = out.kinematic_model_path = torque_actuated_scene(src[:-4] + ".xml" if src.endswith(".mjb") else src, joints=list(cfg.joints))
+    return out
+
+
+def robot_cfg_for(robot: str, torque_actuated: bool = False) -> sim.SimRobotConfig:
+    if torque_actuated:
+        return torque_actuated_cfg(robot_cfg_for(robot))
     if robot == "fr3":
         return default_sim_robot_cfg("fr3_empty_world")
     if robot == "xarm7":
@@ -42,10 +57,12 @@ def robot_cfg_for(robot: str) -> sim.SimRobotConfig:
 def make_vec_env(n_envs: int, async_control: bool, gripper: bool = True, relative: bool = True, control_mode=None, device: int = 0,
                  max_relative_movement=None, robot: str = "fr3", relative_to: str = "last_step", frequency: int = 30,
                  max_convergence_steps: int = 500, robot_cfg: sim.SimRobotConfig | None = None, resolve_robot_contacts=None,
-                 collision_guard: bool = False):
+                 collision_guard: bool = False, torque_actuated: bool = False):
     """`n_envs` environments of one robot type on GPU `device`.  `robot_cfg` overrides the robot's default configuration
     (its scene decides the kernel archetype); only the FR3, SO101 and xarm7_pick scenes carry a gripper.  `collision_guard`: the
-    batched collision guard at its defaults (VecSimEnv.configure_guard; joint-space control only)."""
+    batched collision guard at its defaults (VecSimEnv.configure_guard; joint-space control only).  `torque_actuated`: the scene's
+    torque-actuated variant (every arm actuator a `<motor>`: `SimRobot.set_joint_torque`, `Sim.step_torque`); the env layer's
+    actions stay position commands and do not drive it."""
     cfg = sim.SimConfig(async_control=async_control, realtime=False, frequency=frequency, max_convergence_steps=max_convergence_steps)
     mode = control_mode or ControlMode.JOINTS
     if relative and max_relative_movement is None:
@@ -54,8 +71,11 @@ def make_vec_env(n_envs: int, async_control: bool, gripper: bool = True, relativ
         gripper = False
     gripper_cfg = ((so101_sim_gripper_cfg() if robot == "so101" else xarm7_pick_sim_gripper_cfg() if robot == "xarm7_pick" else default_sim_gripper_cfg())
                    if gripper else None)
+    rcfg = robot_cfg if robot_cfg is not None else robot_cfg_for(robot)
+    if torque_actuated:
+        rcfg = torque_actuated_cfg(rcfg)
     return SimEnvCreator()(
-        mode, robot_cfg if robot_cfg is not None else robot_cfg_for(robot), collision_guard=collision_guard,
+        mode, rcfg, collision_guard=collision_guard,
         gripper_cfg=gripper_cfg,
         sim_cfg=cfg, max_relative_movement=max_relative_movement if relative else None,
         relative_to=RelativeTo.LAST_STEP if relative_to == "last_step" else RelativeTo.CONFIGURED_ORIGIN,

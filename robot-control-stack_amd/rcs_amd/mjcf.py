@@ -999,3 +999,90 @@ def compile_mjcf(path: str | os.PathLike) -> Model:
     if not path.endswith(".xml"):
         raise MjcfError(f"Filetype {os.path.splitext(path)[1]} is unknown (only MJCF .xml is supported)")
     return _Compiler(path).compile()
+
+
+_TORQUE_SCENES: dict[tuple, str] = {}
+_SIDE_FILES = ("collision_vertices.npz", "render_hulls.npz")
+
+
+_TORQUE_SCRATCH: list[str] = []
+
+
+def _torque_scratch_dir() -> str:
+    """This process's scratch directory for the variants written without a destination; removed when the process ends."""
+    import atexit
+    import shutil
+    import tempfile
+
+    if not _TORQUE_SCRATCH:
+        _TORQUE_SCRATCH.append(tempfile.mkdtemp(prefix="rcs_amd_torque_"))
+        atexit.register(shutil.rmtree, _TORQUE_SCRATCH[0], ignore_errors=True)
+    return _TORQUE_SCRATCH[0]
+
+
+def torque_actuated_scene(src_scene_path: str | os.PathLike, dst_dir: str | os.PathLike | None = None, joints=None) -> str:
+    """Write the torque-actuated variant of the scene at ``src_scene_path`` and return its path.
+
+    Every actuator on a joint (the arm's: ``<position>`` or an affine ``<general>``) becomes a ``<motor>`` on the same joint
+    with ``ctrllimited="true"`` and ``ctrlrange`` = the old actuator's ``forcerange`` where it was force-limited, else the
+    joint's ``actuatorfrcrange``; a joint with neither raises :class:`MjcfError`.  Tendon actuators (the gripper), equalities,
+    gravity compensation, damping, armature and friction loss stay as they are.  Includes are expanded into the one file
+    written; the mesh-derived side files are copied beside it.  ``joints``: the names of the arm's joints (None: every joint that
+    carries an actuator; an actuator on a joint outside the list stays as it is).  ``dst_dir`` None: a subdirectory per source scene
+    of this process's scratch directory, which goes when the process ends (the second call returns the first one's file).
+    """
+    import shutil
+
+    src = os.path.abspath(os.fspath(src_scene_path))
+    key = (src, None if joints is None else tuple(joints))
+    if dst_dir is None and key in _TORQUE_SCENES and os.path.exists(_TORQUE_SCENES[key]):
+        return _TORQUE_SCENES[key]
+    comp = _Compiler(src)
+    model = comp.compile()  # (the compiled tables say which range is in force; comp.root is the tree with its includes expanded)
+    elems = [e for act in comp.root.findall("actuator") for e in act]
+    if len(elems) != model.nu:
+        raise MjcfError(f"{src}: {len(elems)} actuator elements for {model.nu} compiled actuators")
+    if joints is not None:
+        unknown = [j for j in joints if j not in model.jnt_names]
+        if unknown:
+            raise MjcfError(f"{src}: no joint named {unknown[0]!r}")
+    A = model.arrays
+    for u, e in enumerate(elems):
+        if A["actuator_trntype"][u] != TRN_JOINT:
+            continue
+        j = int(A["actuator_trnid"][u])
+        if joints is not None and model.jnt_names[j] not in joints:
+            continue
+        if A["actuator_forcelimited"][u]:
+            lo, hi = A["actuator_forcerange"][u]
+        elif A["jnt_actfrclimited"][j]:
+            lo, hi = A["jnt_actfrcrange"][j]
+        else:
+            raise MjcfError(f"joint {model.jnt_names[j]!r}: neither its actuator's forcerange nor its actuatorfrcrange bounds the torque")
+        gear = float(A["actuator_gear"][u])
+        name, joint = e.attrib.get("name"), e.attrib.get("joint", model.jnt_names[j])
+        e.tag = "motor"
+        e.attrib.clear()  # (the class too: its defaults carry the servo's gain and bias)
+        if name is not None:
+            e.set("name", name)
+        e.set("joint", joint)
+        if gear != 1.0:
+            e.set("gear", repr(gear))
+        e.set("ctrllimited", "true")
+        e.set("ctrlrange", f"{float(lo)!r} {float(hi)!r}")
+    if dst_dir is None:
+        dst_dir = os.path.join(_torque_scratch_dir(), f"scene_{len(_TORQUE_SCENES)}")
+        remember = True
+    else:
+        remember = False
+    dst_dir = os.fspath(dst_dir)
+    os.makedirs(dst_dir, exist_ok=True)
+    dst = os.path.join(dst_dir, "scene.xml")
+    ET.ElementTree(comp.root).write(dst)
+    for extra in _SIDE_FILES:
+        f = find_data_file(comp.data_dirs, extra)
+        if f is not None:
+            shutil.copy(f, dst_dir)
+    if remember:
+        _TORQUE_SCENES[key] = dst
+    return dst

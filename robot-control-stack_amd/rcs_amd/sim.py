@@ -205,6 +205,13 @@ class Sim:
         _lib.check(self._L.rcsh_sim_step(self._h, int(k)))
         self._collect_frames()
 
+    def step_torque(self, k: int) -> None:
+        """``k`` substeps of a torque-actuated scene in one launch, the robot's torque law (``SimRobot.configure_torque_law``)
+        evaluated before each of them (rcsh_sim_step_torque)."""
+        if k < 0:
+            raise ValueError("step count must be non-negative")
+        _lib.check(self._L.rcsh_sim_step_torque(self._h, int(k)))
+
     def step_until_convergence(self) -> None:
         _lib.check(self._L.rcsh_sim_step_until_convergence(self._h))
         self._collect_frames()
@@ -488,6 +495,59 @@ class SimRobot:
 
     def get_ik(self):
         return self._ik
+
+    # ---- torque control (include/rcs_hip.h, "torque control"; csrc/torque_team.h)
+    @property
+    def torque_actuated(self) -> bool:
+        """Every arm actuator is a plain torque source (``<motor>``: biastype none, zero biasprm); ``mjcf.torque_actuated_scene``
+        writes such a variant of a shipped scene."""
+        yes = C.c_int32(0)
+        _lib.check(self._L.rcsh_robot_is_torque_actuated(self.sim._h, C.byref(yes)))
+        return bool(yes.value)
+
+    def set_joint_torque(self, tau, mask=None) -> None:
+        """The arm's ``ctrl`` := tau [N, dof] (or [dof]); target, previous angles, flags and the gripper's ctrl stay."""
+        _lib.check(self._L.rcsh_robot_set_joint_torque(self.sim._h, _lib.ptr(self._q(tau)), _lib.ptr(_mask(mask, self.n_envs))))
+
+    def configure_torque_law(self, task_k, task_d, joint_k, joint_d, task_mask: int = 0x3F, damping: float = 0.0, tcp_offset=None,
+                             compensate_bias: bool = True, enabled: bool = True) -> None:
+        """The law ``Sim.step_torque`` evaluates before every substep: ``task_k`` / ``task_d`` [6] (or scalars) on the task
+        acceleration in the base frame, ``joint_k`` / ``joint_d`` [dof] (or scalars) in the null space; ``task_mask`` 0: the pure
+        joint law."""
+        law = _lib.TorqueLaw()
+        law.enabled, law.task_mask, law.damping, law.compensate_bias = int(enabled), int(task_mask), float(damping), int(compensate_bias)
+        off = DeviceKinematics._tcp(tcp_offset)
+        law.tcp_offset7[:] = [0.0] * 7 if off is None else [float(x) for x in off]
+        law.task_k[:] = [float(x) for x in np.broadcast_to(np.asarray(task_k, dtype=np.float64), (6,))]
+        law.task_d[:] = [float(x) for x in np.broadcast_to(np.asarray(task_d, dtype=np.float64), (6,))]
+        jk, jd = np.zeros(8), np.zeros(8)
+        jk[: self.dof] = np.broadcast_to(np.asarray(joint_k, dtype=np.float64), (self.dof,))
+        jd[: self.dof] = np.broadcast_to(np.asarray(joint_d, dtype=np.float64), (self.dof,))
+        law.joint_k[:] = [float(x) for x in jk]
+        law.joint_d[:] = [float(x) for x in jd]
+        _lib.check(self._L.rcsh_torque_configure(self.sim._h, C.byref(law)))
+
+    def set_torque_target(self, pose=None, q=None, mask=None) -> None:
+        """The law's targets: ``pose`` [N, 7] (or [7], or a Pose; base frame) and / or ``q`` [N, dof]; None keeps."""
+        n = self.n_envs
+        if isinstance(pose, common.Pose):
+            pose = pose.as_vec7()
+        p = None if pose is None else np.ascontiguousarray(np.broadcast_to(np.asarray(pose, dtype=np.float64), (n, 7)))
+        qd = None if q is None else self._q(q)
+        _lib.check(self._L.rcsh_torque_set_target(self.sim._h, _lib.ptr(p), _lib.ptr(qd), _lib.ptr(_mask(mask, n))))
+
+    def torque_target(self):
+        """(pose [N, 7], q [N, dof]): the law's targets as they stand."""
+        pose, q = np.zeros((self.n_envs, 7)), np.zeros((self.n_envs, self.dof))
+        _lib.check(self._L.rcsh_torque_get_target(self.sim._h, _lib.ptr(pose), _lib.ptr(q)))
+        return pose, q
+
+    def torque_status(self) -> np.ndarray:
+        """[N] bool: the environment met a singular task-space matrix in a substep since its last reset (that substep kept the
+        torque of the one before)."""
+        out = np.zeros(self.n_envs, dtype=np.uint8)
+        _lib.check(self._L.rcsh_torque_status(self.sim._h, _lib.ptr(out)))
+        return out.astype(bool)
 
     def get_base_pose_in_world_coordinates(self) -> common.Pose:
         out = np.zeros((self.n_envs, 7))
