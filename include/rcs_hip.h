@@ -149,7 +149,10 @@ typedef struct rcsh_gripper_desc {
 } rcsh_gripper_desc;
 
 /* Gymnasium-loop configuration of the fused env-step (reference python/rcs/envs/creators.py:43-128). */
-enum { RCSH_MODE_JOINTS = 0, RCSH_MODE_CARTESIAN_TRPY = 1, RCSH_MODE_CARTESIAN_TQUAT = 2 };
+enum { RCSH_MODE_JOINTS = 0, RCSH_MODE_CARTESIAN_TRPY = 1, RCSH_MODE_CARTESIAN_TQUAT = 2,
+       /* torque-actuated robots (csrc/env_torque_team.h; "torque and impedance control modes" below) */
+       RCSH_MODE_TORQUE = 3, RCSH_MODE_JOINT_IMPEDANCE = 4, RCSH_MODE_CARTESIAN_IMPEDANCE_TRPY = 5,
+       RCSH_MODE_CARTESIAN_IMPEDANCE_TQUAT = 6 };
 enum { RCSH_REL_NONE = 0, RCSH_REL_LAST_STEP = 1, RCSH_REL_CONFIGURED_ORIGIN = 2 };
 typedef struct rcsh_env_desc {
   int32_t control_mode;
@@ -673,7 +676,36 @@ int rcsh_sim_set_state(rcsh_sim* sim, const void* blob);
  * truncated, gripper_collision, contact_overflow, contact_unresolved (the last two: no reference counterpart -- a contact
  * phase ran out of slots / the environment was found in a contact this configuration does not resolve, sticky until reset,
  * see rcsh_sim_contact_unresolved) -- `info` rows are written as one 8-byte word each: the buffer must be 8-byte aligned --;
- * gripper_width[N] (double). */
+ * gripper_width[N] (double).
+ *
+ * Torque and impedance control modes (RCSH_MODE_TORQUE .. RCSH_MODE_CARTESIAN_IMPEDANCE_TQUAT; csrc/env_torque_team.h), for
+ * torque-actuated robots (rcsh_robot_is_torque_actuated).  Action row: TORQUE [dof] joint torques (N m); JOINT_IMPEDANCE [dof]
+ * joint positions; CARTESIAN_IMPEDANCE_TRPY [6] xyzrpy; CARTESIAN_IMPEDANCE_TQUAT [7] xyz + xyzw.  One step is ONE stepping launch
+ * -- the wrappers' action(), the target write and round(1 / frequency / timestep) substeps -- and the handle's observing pass:
+ *   gripper           GripperWrapper.action as in the position modes;
+ *   TORQUE            ctrl[arm] = action, held over the substeps (clamped by ctrlrange in the substep like any ctrl); no law, no
+ *                     relative action space, no 1e-3 gate;
+ *   JOINT_IMPEDANCE   the JOINTS mode's RelativeActionSpace arithmetic and RobotEnv.step's gate; a commanded action becomes the
+ *                     law's q_des, a gated-out one leaves the target; nothing of the position servo's bookkeeping (ctrl, target /
+ *                     previous angles, is_moving / is_arrived) is written;
+ *   CARTESIAN_*       the Cartesian modes' wrapper arithmetic and gate; a commanded pose becomes the law's pose target.  The env
+ *                     layer's poses are those of rcsh_robot_get_cartesian_position: the site composed with the robot's tcp_offset.
+ *                     The law's TCP is the site composed with the INVERSE of its tcp_offset7 (quirk Q7): step and reset return
+ *                     RCSH_ERR_ARG unless both are the same TCP, i.e. unless the law's tcp_offset7 is the inverse of the robot's
+ *                     tcp_offset (all-zero counts as the identity, quaternions are compared up to sign);
+ *   the impedance modes evaluate the law before every substep exactly as rcsh_sim_step_torque does, the singular / non-finite
+ *   hold-back and the sticky `singular` byte included.
+ * rcsh_env_reset in these modes: gripper reset, qpos := qpos0, arm := q_home, qvel := 0, ALL of ctrl := 0 (never q_home: ctrl is a
+ * torque), time and callback timestamps := 0, the sticky contact flags and the `singular` byte cleared, the law's q_des := q_home and
+ * its pose target := the TCP pose there; one substep (under the law; with zero torque in TORQUE mode); the relative-action origin :=
+ * the state after it; the observing pass.  Autoreset uses this reset.  `substeps` reports the substeps of the stepping launch.
+ * `collision` in the info row stays what the flags word holds: no collision detection runs in these modes, contact_unresolved is
+ * the signal.
+ * Refused, changing nothing -- RCSH_ERR_ARG: a robot that is not torque-actuated; a scene rcsh_sim_step_torque refuses (free body,
+ * resolved robot contacts, scheduled cameras, static site -- at configure time and again at every step and reset); async_control = 0;
+ * TORQUE with relative_to != RCSH_REL_NONE; the TCP mismatch; an env step of round(1 / frequency / timestep) < 1 substeps (step and
+ * reset).  RCSH_ERR_STATE: an impedance mode without an enabled law (step and reset); together with the collision guard or the
+ * pick task, in either order.  RCSH_ERR_MODEL: no kernel instance (dry friction on another archetype than rcsh_sim_step_torque's). */
 int rcsh_env_configure(rcsh_sim* sim, const rcsh_env_desc* env);
 int rcsh_env_obs_width(const rcsh_sim* sim);
 int rcsh_env_action_width(const rcsh_sim* sim);

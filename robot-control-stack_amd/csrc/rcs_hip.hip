@@ -28,6 +28,7 @@
 #include "dynamics_grad_team.h"
 #include "opspace_team.h"
 #include "torque_team.h"
+#include "env_torque_team.h"
 #include "guard_team.h"
 #include "episode_team.h"
 
@@ -563,7 +564,10 @@ static_assert(kBoxState <= kStageWidth, "the free body's state passes through th
 static_assert(kPoseWidth <= kTaskWidth, "the box pose comes in through the task rows' slice");
 static_assert(kPoseWidth <= kObsBase, "a forward-kinematics pose goes out through the observations' slice");
 
-int action_width(int mode, int narm) { return mode == RCSH_MODE_JOINTS ? narm : (mode == RCSH_MODE_CARTESIAN_TRPY ? 6 : kPoseWidth); }
+int action_width(int mode, int narm) {
+  if (mode == RCSH_MODE_JOINTS || mode == RCSH_MODE_TORQUE || mode == RCSH_MODE_JOINT_IMPEDANCE) return narm;
+  return mode == RCSH_MODE_CARTESIAN_TRPY || mode == RCSH_MODE_CARTESIAN_IMPEDANCE_TRPY ? 6 : kPoseWidth;
+}
 
 int fits(int width, int slice_width, const char* what) {
   if (width < 0 || width > slice_width) return fail(RCSH_ERR_ARG, std::string(what) + ": wider than its staging slice");
@@ -2422,12 +2426,29 @@ int rcsh_sim_set_state(rcsh_sim* s, const void* blob) {
 
 // ---- fused Gymnasium loop
 
+namespace {
+static_assert(RCSH_MODE_TORQUE == kEnvModeTorque && RCSH_MODE_JOINT_IMPEDANCE == kEnvModeJointImpedance &&
+              RCSH_MODE_CARTESIAN_IMPEDANCE_TRPY == kEnvModeCartImpedanceTrpy && RCSH_MODE_CARTESIAN_IMPEDANCE_TQUAT == kEnvModeCartImpedanceTquat,
+              "csrc/env_torque_team.h restates the control modes it serves");
+bool env_torque_mode(int mode) { return mode >= RCSH_MODE_TORQUE && mode <= RCSH_MODE_CARTESIAN_IMPEDANCE_TQUAT; }
+}  // namespace
+
 int rcsh_env_configure(rcsh_sim* s, const rcsh_env_desc* env) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!env) return fail(RCSH_ERR_ARG, "null env description");
-  if (env->control_mode < RCSH_MODE_JOINTS || env->control_mode > RCSH_MODE_CARTESIAN_TQUAT)
+  if (env->control_mode < RCSH_MODE_JOINTS || env->control_mode > RCSH_MODE_CARTESIAN_IMPEDANCE_TQUAT)
     return fail(RCSH_ERR_ARG, "bad control_mode");
   if (env->relative_to < 0 || env->relative_to > 2) return fail(RCSH_ERR_ARG, "bad relative_to");
+  if (env_torque_mode(env->control_mode)) {
+    // the torque and impedance modes (csrc/env_torque_team.h): every refusal before anything is written
+    if (s->guard.enabled) return fail(RCSH_ERR_STATE, "the collision guard is enabled and guards position commands only: disable it (rcsh_env_configure_guard) before configuring a torque / impedance control mode");
+    if (s->task.pick_cube) return fail(RCSH_ERR_STATE, "the pick task is configured: it is not built for the torque / impedance control modes");
+    if (const std::string why = torque_scope(s); !why.empty()) return fail(RCSH_ERR_ARG, "torque / impedance control mode: " + why);
+    if (!s->sim.async_control) return fail(RCSH_ERR_ARG, "torque / impedance control mode: async_control = 0 steps until convergence, and the convergence predicates assume position servos");
+    if (env->control_mode == RCSH_MODE_TORQUE && env->relative_to != RCSH_REL_NONE)
+      return fail(RCSH_ERR_ARG, "RCSH_MODE_TORQUE has no relative action space: relative_to must be RCSH_REL_NONE");
+    if (int rc = torque_buffers(s)) return rc;
+  }
   if (s->guard.enabled && env->control_mode != RCSH_MODE_JOINTS)
     return fail(RCSH_ERR_STATE, "the collision guard is enabled and guards joint-space actions only: disable it (rcsh_env_configure_guard) before configuring a Cartesian control mode");
   s->env.mode = env->control_mode;
@@ -2479,6 +2500,99 @@ int episode_clear(rcsh_sim* s, const uint8_t* mask_dev) {
   HIP_TRY(hipGetLastError());
   return RCSH_OK;
 }
+// ---- the torque and impedance control modes (csrc/env_torque_team.h)
+// The law's TCP is the site composed with the INVERSE of its tcp_offset7 (quirk Q7), the env layer's the site composed with the robot's
+// tcp_offset: the same TCP when offset7 * tcp is the identity (all-zero offset7: the identity; the quaternion up to sign).
+bool env_torque_same_tcp(const rcsh_sim* s) {
+  const double* o = s->tq.law.tcp_offset7;
+  Pose a, b, c;
+  const double nq = std::sqrt(o[3] * o[3] + o[4] * o[4] + o[5] * o[5] + o[6] * o[6]);
+  const double ident[4] = {0, 0, 0, 1}, zero[3] = {0, 0, 0};
+  if (nq > 0.0) {
+    const double qn[4] = {o[3] / nq, o[4] / nq, o[5] / nq, o[6] / nq};
+    pose_from_quat(qn, o, a);
+  } else {
+    pose_from_quat(ident, zero, a);
+  }
+  const double* r = s->robot.tcp;
+  const double nr = std::sqrt(r[3] * r[3] + r[4] * r[4] + r[5] * r[5] + r[6] * r[6]);
+  if (nr > 0.0) {
+    const double qn[4] = {r[3] / nr, r[4] / nr, r[5] / nr, r[6] / nr};
+    pose_from_quat(qn, r, b);
+  } else {
+    pose_from_quat(ident, r, b);
+  }
+  pose_mul(a, b, c);
+  constexpr double kTol = 1e-12;  // (round-off of one pose product; a metre-sized offset differs by far more)
+  const double sg = c.q[3] < 0.0 ? -1.0 : 1.0;
+  return std::fabs(c.t[0]) <= kTol && std::fabs(c.t[1]) <= kTol && std::fabs(c.t[2]) <= kTol && std::fabs(c.q[0]) <= kTol &&
+         std::fabs(c.q[1]) <= kTol && std::fabs(c.q[2]) <= kTol && std::fabs(sg * c.q[3] - 1.0) <= kTol;
+}
+// why a step or reset in a torque / impedance mode is refused now (RCSH_OK: it is not); nothing has been written when it is
+int env_torque_ready(rcsh_sim* s, const char* what) {
+  const int mode = s->env.mode;
+  if (const std::string why = torque_scope(s); !why.empty()) return fail(RCSH_ERR_ARG, std::string(what) + ": " + why);
+  if (!s->sim.async_control) return fail(RCSH_ERR_ARG, std::string(what) + ": async_control = 0 in a torque / impedance control mode");
+  if (s->guard.enabled) return fail(RCSH_ERR_STATE, std::string(what) + ": the collision guard is enabled in a torque / impedance control mode");
+  if (s->task.pick_cube) return fail(RCSH_ERR_STATE, std::string(what) + ": the pick task is configured in a torque / impedance control mode");
+  // (k_env_torque parks the site frame in its substeps: a step of none would leave the observing pass and the next origin a zero frame)
+  if (std::nearbyint(1.0 / s->sim.frequency / s->dm.timestep) < 1.0)
+    return fail(RCSH_ERR_ARG, std::string(what) + ": round(1 / frequency / timestep) is zero substeps an env step in a torque / impedance control mode");
+  if (mode != RCSH_MODE_TORQUE && !s->tq.law.enabled)
+    return fail(RCSH_ERR_STATE, std::string(what) + ": the impedance control modes need an enabled torque law (rcsh_torque_configure)");
+  if ((mode == RCSH_MODE_CARTESIAN_IMPEDANCE_TRPY || mode == RCSH_MODE_CARTESIAN_IMPEDANCE_TQUAT) && !env_torque_same_tcp(s))
+    return fail(RCSH_ERR_ARG, std::string(what) + ": the law's tcp_offset7 and the robot's tcp_offset do not describe the same TCP (the law's TCP is the "
+                              "site composed with the INVERSE of tcp_offset7: configure the inverse of the robot's tcp_offset)");
+  if (s->dm.has_friction && !(s->narm == 7 && !s->grip))
+    return fail(RCSH_ERR_MODEL, std::string(what) + ": no kernel instantiated for this archetype with dry joint friction");
+  return torque_buffers(s);
+}
+// the ONE stepping launch of a step (action_dev) or a reset (do_reset, mask_dev) in a torque / impedance mode
+int env_torque_launch(rcsh_sim* s, bool do_reset, const uint8_t* mask_dev, const double* action_dev, const float* gripper_dev, int32_t* substeps_dev) {
+  Params P = make_params(s);
+  const int mode = s->env.mode;
+  // (cart_prepare reads the position mode of the same action row)
+  P.env.mode = mode == RCSH_MODE_CARTESIAN_IMPEDANCE_TRPY ? RCSH_MODE_CARTESIAN_TRPY
+               : mode == RCSH_MODE_CARTESIAN_IMPEDANCE_TQUAT ? RCSH_MODE_CARTESIAN_TQUAT : RCSH_MODE_JOINTS;
+  // RobotSimWrapper.step (reference python/rcs/envs/sim.py:49-59); Python's round(): half to even
+  const int32_t k = (int32_t)std::nearbyint(1.0 / s->sim.frequency / s->dm.timestep);
+  const TorqueArgs A = torque_args(s, s->tq.law, k);
+  EnvTorqueOp op{};
+  op.mode = mode;
+  op.do_reset = do_reset ? 1 : 0;
+  op.mask = mask_dev;
+  op.action = action_dev;
+  op.gripper = gripper_dev;
+  op.substeps = substeps_dev;
+  bool launched = false;
+  int rc = team_launch(s, s->n, "env step (torque / impedance)", [&](auto topo, dim3 grid, dim3 block) {
+    using T = decltype(topo);
+    if (!s->dm.has_friction) {
+      hipLaunchKernelGGL((k_env_torque<T, false>), grid, block, 0, s->stream, P, op, A);
+      launched = true;
+    } else if constexpr (T::NARM == 7 && !T::GRIP) {
+      hipLaunchKernelGGL((k_env_torque<T, true>), grid, block, 0, s->stream, P, op, A);
+      launched = true;
+    }
+  });
+  if (rc) return rc;
+  if (!launched) return fail(RCSH_ERR_MODEL, "env step (torque / impedance): no kernel instantiated for this archetype with dry joint friction");
+  return RCSH_OK;
+}
+// the handle's observing pass behind that launch: observation, info and gripper width of the masked environments, and the check for
+// contacts nobody resolves at the handle's cadence -- so contact_unresolved belongs to the step that reports it
+int env_torque_observe(rcsh_sim* s, const uint8_t* mask_dev, double* obs_dev, uint8_t* info_dev, double* gw_dev) {
+  RunOp op{};
+  op.nsteps = 0;
+  op.observe_only = 1;
+  op.write_obs = obs_dev != nullptr;
+  op.check = s->contact_check && s->check_every > 0 && (s->check_seq++ % s->check_every) == 0;
+  op.mask = mask_dev;
+  op.obs = obs_dev; op.info = info_dev; op.gripper_width = gw_dev;
+  if (!op.write_obs && !op.check) return RCSH_OK;
+  return launch_run(s, op, false);
+}
+
 // What follows the stepping launch of a step under autoreset: k_episode_end over the step's outputs, then the masked reset launch
 // (rcsh_env_reset_dev's, or rcsh_env_reset_task_dev's with the poses just drawn) with `done` as its mask -- always enqueued, the host
 // does not know who is done --, writing the new episodes' first observation into the step's own obs / gripper_width rows.
@@ -2498,14 +2612,20 @@ int episode_end(rcsh_sim* s, double* obs, uint8_t* info, double* gw, const doubl
   A.draw = episode_draw_of(a);
   hipLaunchKernelGGL(k_episode_end, dim3((s->n + A.envs_per_block - 1) / A.envs_per_block), dim3(kEpisodeBlock), 0, s->stream, A);
   HIP_TRY(hipGetLastError());
-  RunOp op{};
-  op.do_reset = 1;
-  op.nsteps = 1;
-  op.write_obs = 1;
-  op.mask = r.done;
-  op.box_qpos = A.draw_box ? r.reset_box_qpos : nullptr;
-  op.obs = obs; op.info = r.reset_info; op.gripper_width = gw;
-  int rc = launch_run(s, op, false);
+  int rc = RCSH_OK;
+  if (env_torque_mode(s->env.mode)) {  // (the reset form of k_env_torque, then the observing pass, both under `done`)
+    rc = env_torque_launch(s, true, r.done, nullptr, nullptr, nullptr);
+    if (!rc) rc = env_torque_observe(s, r.done, obs, r.reset_info, gw);
+  } else {
+    RunOp op{};
+    op.do_reset = 1;
+    op.nsteps = 1;
+    op.write_obs = 1;
+    op.mask = r.done;
+    op.box_qpos = A.draw_box ? r.reset_box_qpos : nullptr;
+    op.obs = obs; op.info = r.reset_info; op.gripper_width = gw;
+    rc = launch_run(s, op, false);
+  }
   if (rc) return rc;
   s->episode_stepped = true;
   s->episode_host_valid = false;
@@ -2597,6 +2717,12 @@ int env_reset_launch(rcsh_sim* s, const uint8_t* mask_dev, const double* box_qpo
 int rcsh_env_reset_dev(rcsh_sim* s, const uint8_t* mask_dev, double* obs_dev, uint8_t* info_dev, double* gw_dev) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!s->env_configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure first");
+  if (env_torque_mode(s->env.mode)) {
+    int rc = env_torque_ready(s, "env reset");
+    if (!rc) rc = env_torque_launch(s, true, mask_dev, nullptr, nullptr, nullptr);
+    if (!rc) rc = env_torque_observe(s, mask_dev, obs_dev, info_dev, gw_dev);
+    return rc ? rc : episode_clear(s, mask_dev);
+  }
   return env_reset_launch(s, mask_dev, nullptr, obs_dev, info_dev, gw_dev);
 }
 
@@ -2667,6 +2793,8 @@ int rcsh_env_configure_guard(rcsh_sim* s, const rcsh_guard_desc* g) {
   if (!g) return fail(RCSH_ERR_ARG, "null guard description");
   if (g->kinds < 1 || g->kinds > kQueryKinds) return fail(RCSH_ERR_ARG, "the guard's kinds mask must select at least one of bit 0 floor, 1 self, 2 free body, and nothing else");
   if (!(g->resolution > 0.0) || !std::isfinite(g->resolution)) return fail(RCSH_ERR_ARG, "resolution must be positive and finite");
+  if (env_torque_mode(s->env.mode))
+    return fail(RCSH_ERR_STATE, "the collision guard guards position commands only: the environments are configured for a torque / impedance control mode");
   if (s->env.mode != RCSH_MODE_JOINTS)
     return fail(RCSH_ERR_STATE, "the collision guard guards joint-space actions only: the environments are configured for a Cartesian control mode");
   int rc = query_check(s, s->n, g->kinds, nullptr);
@@ -2691,7 +2819,10 @@ int rcsh_env_configure_guard(rcsh_sim* s, const rcsh_guard_desc* g) {
 int rcsh_env_guard_peek_dev(rcsh_sim* s, const double* action_dev, int32_t* result_dev, double* t_contact_dev, uint8_t* blocked_dev) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!s->guard.configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure_guard first");
-  if (s->env.mode != RCSH_MODE_JOINTS) return fail(RCSH_ERR_STATE, "the collision guard answers for joint-space actions only: the environments are configured for a Cartesian control mode");
+  if (s->env.mode != RCSH_MODE_JOINTS)
+    return fail(RCSH_ERR_STATE, env_torque_mode(s->env.mode)
+                                    ? "the collision guard answers for joint-space position commands only: the environments are configured for a torque / impedance control mode"
+                                    : "the collision guard answers for joint-space actions only: the environments are configured for a Cartesian control mode");
   if (!action_dev || !result_dev || !t_contact_dev || !blocked_dev) return fail(RCSH_ERR_ARG, "null argument");
   return guard_launch(s, action_dev, result_dev, t_contact_dev, blocked_dev, nullptr);
 }
@@ -2699,7 +2830,10 @@ int rcsh_env_guard_peek_dev(rcsh_sim* s, const double* action_dev, int32_t* resu
 int rcsh_env_guard_peek(rcsh_sim* s, const double* action, int32_t* result, double* t_contact, uint8_t* blocked) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!s->guard.configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure_guard first");
-  if (s->env.mode != RCSH_MODE_JOINTS) return fail(RCSH_ERR_STATE, "the collision guard answers for joint-space actions only: the environments are configured for a Cartesian control mode");
+  if (s->env.mode != RCSH_MODE_JOINTS)
+    return fail(RCSH_ERR_STATE, env_torque_mode(s->env.mode)
+                                    ? "the collision guard answers for joint-space position commands only: the environments are configured for a torque / impedance control mode"
+                                    : "the collision guard answers for joint-space actions only: the environments are configured for a Cartesian control mode");
   if (!action) return fail(RCSH_ERR_ARG, "null action");
   const size_t n = (size_t)s->n, na = n * (size_t)s->narm;
   int rc = query_finite(action, na, "action");
@@ -2743,6 +2877,9 @@ int rcsh_env_step_dev(rcsh_sim* s, const double* action_dev, const float* grippe
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!s->env_configured) return fail(RCSH_ERR_STATE, "call rcsh_env_configure first");
   if (!action_dev) return fail(RCSH_ERR_ARG, "null action");
+  if (env_torque_mode(s->env.mode)) {
+    if (int rc = env_torque_ready(s, "env step")) return rc;
+  }
   double* task_dev = s->pending_task;
   const bool autoreset = s->autoreset.enabled;
   if (autoreset) {  // (k_episode_end reads the step's outputs: an output the caller does not ask for goes to the staging slice)
@@ -2751,6 +2888,13 @@ int rcsh_env_step_dev(rcsh_sim* s, const double* action_dev, const float* grippe
     if (!info_dev) info_dev = st.info;
     if (!gw_dev) gw_dev = st.grip_width;
     if (!task_dev && s->task.pick_cube) task_dev = st.box_task;
+  }
+  if (env_torque_mode(s->env.mode)) {
+    // one stepping launch -- action arithmetic, target write, substeps --, then the observing pass
+    int rc = env_torque_launch(s, false, nullptr, action_dev, gripper_dev, substeps_dev);
+    if (!rc) rc = env_torque_observe(s, nullptr, obs_dev, info_dev, gw_dev);
+    if (rc) return rc;
+    return autoreset ? episode_end(s, obs_dev, info_dev, gw_dev, task_dev) : (int)RCSH_OK;
   }
   RunOp op{};
   op.apply_action = 1;
@@ -2797,6 +2941,7 @@ int rcsh_env_configure_pick_task(rcsh_sim* s, const rcsh_pick_task_desc* t) {
   REQUIRE_SIM(s); REQUIRE_ROBOT(s);
   if (!t) return fail(RCSH_ERR_ARG, "null task description");
   if (!s->box.present) return fail(RCSH_ERR_STATE, "the pick task needs the scene's free box: call rcsh_sim_add_free_box first");
+  if (s->env_configured && env_torque_mode(s->env.mode)) return fail(RCSH_ERR_STATE, "the pick task is not built for the torque / impedance control modes");
   s->task.pick_cube = 1;
   for (int k = 0; k < 3; ++k) s->task.ee_home[k] = t->ee_home[k];
   s->task.success_z = t->success_height;

@@ -16,6 +16,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RCSH_LIB") or os.path.join(_HERE, "librcs_hip.so")  # (RCSH_LIB: a development build, for A/B measurements)
 
 RCSH_OK, RCSH_ERR_ARG, RCSH_ERR_NAME, RCSH_ERR_MODEL, RCSH_ERR_DEVICE, RCSH_ERR_STATE = range(6)
+# rcsh_env_desc.control_mode / relative_to (include/rcs_hip.h)
+RCSH_MODE_JOINTS, RCSH_MODE_CARTESIAN_TRPY, RCSH_MODE_CARTESIAN_TQUAT = 0, 1, 2
+RCSH_MODE_TORQUE, RCSH_MODE_JOINT_IMPEDANCE, RCSH_MODE_CARTESIAN_IMPEDANCE_TRPY, RCSH_MODE_CARTESIAN_IMPEDANCE_TQUAT = 3, 4, 5, 6
+RCSH_REL_NONE, RCSH_REL_LAST_STEP, RCSH_REL_CONFIGURED_ORIGIN = 0, 1, 2
 
 _I32P = C.POINTER(C.c_int32)
 _F64P = C.POINTER(C.c_double)

@@ -7,6 +7,11 @@ class ControlMode(Enum):
     JOINTS = auto()
     CARTESIAN_TRPY = auto()
     CARTESIAN_TQuat = auto()
+    # torque-actuated robots (csrc/env_torque_team.h; no reference counterpart): appended, the members above keep their values
+    TORQUE = auto()
+    JOINT_IMPEDANCE = auto()
+    CARTESIAN_IMPEDANCE_TRPY = auto()
+    CARTESIAN_IMPEDANCE_TQuat = auto()
 
 
 class RelativeTo(Enum):

@@ -18,9 +18,18 @@ import numpy as np
 from .. import _lib, common, sim
 from .base import ControlMode, RelativeTo
 
-_MODE = {ControlMode.JOINTS: 0, ControlMode.CARTESIAN_TRPY: 1, ControlMode.CARTESIAN_TQuat: 2}
+_MODE = {ControlMode.JOINTS: _lib.RCSH_MODE_JOINTS, ControlMode.CARTESIAN_TRPY: _lib.RCSH_MODE_CARTESIAN_TRPY,
+         ControlMode.CARTESIAN_TQuat: _lib.RCSH_MODE_CARTESIAN_TQUAT, ControlMode.TORQUE: _lib.RCSH_MODE_TORQUE,
+         ControlMode.JOINT_IMPEDANCE: _lib.RCSH_MODE_JOINT_IMPEDANCE,
+         ControlMode.CARTESIAN_IMPEDANCE_TRPY: _lib.RCSH_MODE_CARTESIAN_IMPEDANCE_TRPY,
+         ControlMode.CARTESIAN_IMPEDANCE_TQuat: _lib.RCSH_MODE_CARTESIAN_IMPEDANCE_TQUAT}
 _REL = {None: 0, RelativeTo.LAST_STEP: 1, RelativeTo.CONFIGURED_ORIGIN: 2}
-_ACTION_KEY = {ControlMode.JOINTS: "joints", ControlMode.CARTESIAN_TRPY: "xyzrpy", ControlMode.CARTESIAN_TQuat: "tquat"}
+_ACTION_KEY = {ControlMode.JOINTS: "joints", ControlMode.CARTESIAN_TRPY: "xyzrpy", ControlMode.CARTESIAN_TQuat: "tquat",
+               ControlMode.TORQUE: "torque", ControlMode.JOINT_IMPEDANCE: "joints", ControlMode.CARTESIAN_IMPEDANCE_TRPY: "xyzrpy",
+               ControlMode.CARTESIAN_IMPEDANCE_TQuat: "tquat"}
+# the torque and impedance modes of torque-actuated robots (csrc/env_torque_team.h)
+TORQUE_MODES = (ControlMode.TORQUE, ControlMode.JOINT_IMPEDANCE, ControlMode.CARTESIAN_IMPEDANCE_TRPY, ControlMode.CARTESIAN_IMPEDANCE_TQuat)
+_JOINT_ROW_MODES = (ControlMode.JOINTS, ControlMode.TORQUE, ControlMode.JOINT_IMPEDANCE)
 
 DEFAULT_MAX_CART_MOV = 0.5  # reference base.py:366-368
 DEFAULT_MAX_CART_ROT = np.deg2rad(90)
@@ -64,7 +73,7 @@ class VecSimEnv:
         max_mov = [0.0, 0.0]
         if max_relative_movement is not None:
             rel = _REL[relative_to]
-            if control_mode == ControlMode.JOINTS:
+            if control_mode in _JOINT_ROW_MODES:
                 assert isinstance(max_relative_movement, float), "joint-space max_mov must be a float (rad)"
                 max_mov = [float(max_relative_movement), 0.0]
             elif isinstance(max_relative_movement, tuple):
@@ -430,6 +439,10 @@ class VecSimEnv:
         # (no reference counterpart) the environment's geoms were found in a contact this configuration does not resolve, since its
         # last reset (csrc/check_team.h): MuJoCo would have resolved it, so from that step on the trajectory is not MuJoCo's
         i["contact_unresolved"] = info[:, 7].astype(bool)
+        if self.control_mode in TORQUE_MODES:
+            # (no reference counterpart) the law met a singular task-space matrix, or a non-finite torque, in a substep since the
+            # environment's last reset: that substep kept the torque of the one before (SimRobot.torque_status)
+            i["torque_singular"] = self.robot.torque_status()
         self._after_step(info)
         truncated = info[:, 4].astype(bool)  # (a truncating guard has set it for the environments it blocked)
         terminated = np.zeros(n, dtype=bool)
@@ -602,15 +615,33 @@ def random_object_qpos(init_object_pose: common.Pose, n_envs: int, include_posit
 class SimEnvCreator:
     """Reference python/rcs/envs/creators.py:43-128 for N environments.  ``collision_guard=True`` returns the env with the batched
     collision guard configured at its defaults (:meth:`VecSimEnv.configure_guard`: a kinematic, certifying guard decided on the
-    device, in place of the reference's shadow simulation); it needs a joint-space control mode."""
+    device, in place of the reference's shadow simulation); it needs a joint-space control mode.
+
+    The torque and impedance modes (``ControlMode.TORQUE``, ``JOINT_IMPEDANCE``, ``CARTESIAN_IMPEDANCE_TRPY`` / ``_TQuat``; no reference
+    counterpart) need a torque-actuated scene (``robot_cfg`` from :func:`rcs_amd.envs.factory.torque_actuated_cfg`) and, for the
+    impedance modes, ``torque_law=dict(...)``: the keyword arguments of :meth:`rcs_amd.sim.SimRobot.configure_torque_law`, passed on
+    before the env is configured.  For the Cartesian modes the law's ``tcp_offset`` defaults to the robot configuration's TCP: the law
+    composes the site with the INVERSE of its offset (reference quirk Q7), so the default is ``robot_cfg.tcp_offset.inverse()``.  The
+    ``Sim`` is created with ``resolve_robot_contacts=False`` (the fused torque launch resolves no contacts; ``True`` is an error) and
+    the env reports unresolved contacts instead of switching modes (``on_unresolved_contact = "flag"``)."""
 
     def __call__(self, control_mode: ControlMode, robot_cfg: sim.SimRobotConfig, collision_guard: bool = False,
                  gripper_cfg: sim.SimGripperConfig | None = None, sim_cfg: sim.SimConfig | None = None,
                  hand_cfg=None, cameras=None, max_relative_movement: float | tuple[float, float] | None = None,
                  relative_to: RelativeTo = RelativeTo.LAST_STEP, sim_wrapper=None, n_envs: int = 1, device: int = 0,
-                 resolve_robot_contacts=None) -> VecSimEnv:
+                 resolve_robot_contacts=None, torque_law: dict | None = None) -> VecSimEnv:
         if hand_cfg is not None or sim_wrapper is not None:
             raise NotImplementedError("hands and sim_wrapper are outside this backend's hot path")
+        torque_mode = control_mode in TORQUE_MODES
+        if torque_mode:
+            if collision_guard:
+                raise NotImplementedError("collision_guard guards position commands only: it is not built for the torque and impedance modes")
+            if resolve_robot_contacts:
+                raise ValueError("resolve_robot_contacts=True with a torque / impedance control mode: the fused torque launch "
+                                 "(csrc/env_torque_team.h) resolves no contacts; unresolved contacts are reported in info['contact_unresolved']")
+            resolve_robot_contacts = False
+        elif torque_law is not None:
+            raise ValueError("torque_law configures the torque and impedance control modes only")
         if collision_guard and control_mode != ControlMode.JOINTS:
             raise NotImplementedError("collision_guard guards joint-space actions only (ControlMode.JOINTS): the Cartesian modes' IK runs in a "
                                       "launch of its own, and a guard between it and the stepping launch is not built yet")
@@ -622,7 +653,14 @@ class SimEnvCreator:
             from ..camera import SimCameraSet
 
             camera_set = SimCameraSet(simulation, cameras, physical_units=True, render_on_demand=True)
+        if torque_mode and torque_law is not None:
+            law = dict(torque_law)
+            if control_mode in (ControlMode.CARTESIAN_IMPEDANCE_TRPY, ControlMode.CARTESIAN_IMPEDANCE_TQuat) and law.get("tcp_offset") is None:
+                law["tcp_offset"] = robot_cfg.tcp_offset.inverse()  # (quirk Q7: the law's TCP is site * offset^-1, the env layer's site * tcp_offset)
+            robot.configure_torque_law(**law)
         venv = VecSimEnv(simulation, robot, gripper, control_mode, max_relative_movement, relative_to, camera_set=camera_set)
+        if torque_mode:
+            venv.on_unresolved_contact = "flag"
         if collision_guard:
             venv.configure_guard()
         return venv

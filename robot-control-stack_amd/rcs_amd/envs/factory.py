@@ -57,14 +57,20 @@ def robot_cfg_for(robot: str, torque_actuated: bool = False) -> sim.SimRobotConf
 def make_vec_env(n_envs: int, async_control: bool, gripper: bool = True, relative: bool = True, control_mode=None, device: int = 0,
                  max_relative_movement=None, robot: str = "fr3", relative_to: str = "last_step", frequency: int = 30,
                  max_convergence_steps: int = 500, robot_cfg: sim.SimRobotConfig | None = None, resolve_robot_contacts=None,
-                 collision_guard: bool = False, torque_actuated: bool = False):
+                 collision_guard: bool = False, torque_actuated: bool = False, torque_law: dict | None = None):
     """`n_envs` environments of one robot type on GPU `device`.  `robot_cfg` overrides the robot's default configuration
     (its scene decides the kernel archetype); only the FR3, SO101 and xarm7_pick scenes carry a gripper.  `collision_guard`: the
     batched collision guard at its defaults (VecSimEnv.configure_guard; joint-space control only).  `torque_actuated`: the scene's
-    torque-actuated variant (every arm actuator a `<motor>`: `SimRobot.set_joint_torque`, `Sim.step_torque`); the env layer's
-    actions stay position commands and do not drive it."""
+    torque-actuated variant (every arm actuator a `<motor>`: `SimRobot.set_joint_torque`, `Sim.step_torque`).  The env layer drives
+    it in the control modes `ControlMode.TORQUE` (action `"torque"`: joint torques; no relative action space, `relative` is ignored),
+    `JOINT_IMPEDANCE` (`"joints"`), `CARTESIAN_IMPEDANCE_TRPY` (`"xyzrpy"`) and `CARTESIAN_IMPEDANCE_TQuat` (`"tquat"`), whose actions
+    become the targets of the substep-rate law given as `torque_law=dict(...)` (the keyword arguments of
+    `SimRobot.configure_torque_law`; SimEnvCreator); these modes need `torque_actuated=True` and `async_control=True`.  In the
+    position modes the actions of such an env stay position commands and do not drive it."""
     cfg = sim.SimConfig(async_control=async_control, realtime=False, frequency=frequency, max_convergence_steps=max_convergence_steps)
     mode = control_mode or ControlMode.JOINTS
+    if mode == ControlMode.TORQUE:
+        relative = False
     if relative and max_relative_movement is None:
         max_relative_movement = MAX_JOINT_MOV
     if not (robot.startswith("fr3") or robot in ("so101", "xarm7_pick")):
@@ -79,5 +85,5 @@ def make_vec_env(n_envs: int, async_control: bool, gripper: bool = True, relativ
         gripper_cfg=gripper_cfg,
         sim_cfg=cfg, max_relative_movement=max_relative_movement if relative else None,
         relative_to=RelativeTo.LAST_STEP if relative_to == "last_step" else RelativeTo.CONFIGURED_ORIGIN,
-        n_envs=n_envs, device=device, resolve_robot_contacts=resolve_robot_contacts,
+        n_envs=n_envs, device=device, resolve_robot_contacts=resolve_robot_contacts, torque_law=torque_law,
     )
